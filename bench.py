@@ -1,6 +1,13 @@
 """Benchmark: LightGCN propagation + BPR training step on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config C4]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times exactly --steps steps, counts the gathered
+edges of the value over --count-steps steps, writes the last timed step's
+outputs (--dump-outputs) and prints the result line. Everything else described
+below (roofline, dense step, CPU baseline, stock-torch and drop-in steps, the
+all-reduce probe and the runs beside an N > 1 line) is measured with --full.
 
 A "step" is one full training step of Version-2/lighgcn_cu_pop.py:826-866 on
 one batch: pop-mix sampling -> K-layer GS propagation (2K fused SpMMs) ->
@@ -498,6 +505,60 @@ def step_summary(ms, dense_ms, torch_ref, dropin, dropin_fused, dropin_bwd) -> d
                     "FusedAdam / FusedAdam(fuse_backward=True)"}
 
 
+# keys of the result line that only a --full run measures
+FULL_ONLY_KEYS = ("roofline_per_kernel", "torch_gpu_reference", "dropin_module_step",
+                  "dropin_fused_adam_step", "dropin_backward_adam_step", "weak_beside",
+                  "partition_beside", "chain_beside", "allreduce_probe", "chain_rule",
+                  "dense_ms_per_step", "dense_edges_per_s", "dense_note", "spmm_ms_per_step",
+                  "roofline", "cpu_baseline")
+
+# --dump-outputs: bytes of sampled embedding rows kept per table (the tables of
+# C4 are 1.3 GB / 0.26 GB; the whole dump stays far below 64 MB)
+DUMP_TABLE_BYTES = 8 << 20
+DUMP_SEED = 20240
+
+
+def collect_outputs(trainer, loss, dist_mode: bool) -> dict:
+    """What a caller of the timed step holds after its last call, as host
+    arrays: the loss, the batch (input ids) and the updated embedding tables at
+    the batch's rows and at a fixed, seeded sample of rows (input ids, so the
+    vertex order inside the graph does not matter). Sharded trainers (their
+    tables are collective to gather) give the loss alone."""
+    out = {"loss": loss.detach().float().reshape(1).cpu().numpy()}
+    if dist_mode:
+        return out
+    users, pos, neg = trainer.batch()
+    rng = np.random.default_rng(DUMP_SEED)
+    n = max(1, DUMP_TABLE_BYTES // (4 * trainer.d))
+    rows = {"user": np.sort(rng.choice(trainer.U, size=min(n, trainer.U), replace=False)),
+            "item": np.sort(rng.choice(trainer.I, size=min(n, trainer.I), replace=False))}
+    tables = {"user": (trainer.user_w, trainer.graph.user_order),
+              "item": (trainer.item_w, trainer.graph.item_order)}
+
+    def take(side: str, ids: torch.Tensor) -> np.ndarray:
+        table, order = tables[side]
+        ids = ids.to(device=table.device, dtype=torch.int64)
+        if order is not None:
+            ids = order.to_internal(ids)
+        return table[ids.long()].float().cpu().numpy()
+
+    for name, ids in (("batch_users", users), ("batch_pos", pos), ("batch_neg", neg)):
+        out[name] = ids.cpu().numpy().astype(np.float64)
+    out["user_emb_batch"] = take("user", users)
+    out["item_emb_pos"] = take("item", pos)
+    out["item_emb_neg"] = take("item", neg)
+    for side in ("user", "item"):
+        out[f"{side}_sample_rows"] = rows[side].astype(np.float64)
+        out[f"{side}_emb_sample"] = take(side, torch.from_numpy(rows[side]))
+    return out
+
+
+def write_outputs(path: str, arrays: dict) -> None:
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def main():
     global cfg_name_global
     out_stream = _quiet_stdout()
@@ -506,6 +567,18 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", default="C4")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline figure: per-kernel "
+                         "roofline events, the dense step, the CPU baseline, the stock-torch "
+                         "and drop-in steps, and at N > 1 the all-reduce probe and the "
+                         "partition / chain / weak runs beside the line (each still has its "
+                         "own switch below). Without it a run sets up, warms up, times "
+                         "--steps steps, counts the value's edges and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step left a "
+                         "caller as DIR/<name>.npy (float32 / float64): loss, the batch, the "
+                         "updated embedding rows of the batch and of a fixed seeded sample "
+                         "of rows (sharded runs: rank 0's loss)")
     ap.add_argument("--variant", default="v2_pop")
     ap.add_argument("--cred", default="beta", choices=["beta", "ones"])
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -589,6 +662,10 @@ def main():
                          "ranges (the metric's |E|); weak = every rank owns a full "
                          "config-sized user shard over the shared items")
     args = ap.parse_args()
+    if not args.full:   # a plain run: only what the headline figure needs
+        args.no_cpu_baseline = args.no_torch_reference = True
+        args.dense_check = args.weak_beside = args.ar_probe = 0
+        args.partition_beside = args.chain_beside = 0
     cfg_name_global = args.config
     cfg = CONFIGS[args.config]
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -761,7 +838,8 @@ def main():
         # `--roofline-steps` extra steps right after the timed region instead.
         # A captured graph replays its launches without the host: its per-launch
         # events are taken over eager steps after the timed region, as for sharded.
-        events_in_loop = not dist_mode and not use_graph
+        # (--full only: a plain run times its steps with no events in them)
+        events_in_loop = args.full and not dist_mode and not use_graph
         if events_in_loop:
             P.set_spmm_timer(dom_timer)
         # rocprofv3 runs (tools/profile_box.sh) cut the trace at two empty marker
@@ -779,12 +857,15 @@ def main():
             torch.distributed.barrier()
         elapsed = time.perf_counter() - t0
         P.set_spmm_timer(None)
+        # the last timed step's results, copied out before any later step
+        outputs = collect_outputs(trainer, loss, dist_mode) if args.dump_outputs else None
         timer_steps = max(1, args.roofline_steps)
-        P.set_spmm_timer(timer)
-        for _ in range(timer_steps):
-            trainer.step()
-        torch.cuda.synchronize()
-        P.set_spmm_timer(None)
+        if args.full:
+            P.set_spmm_timer(timer)
+            for _ in range(timer_steps):
+                trainer.step()
+            torch.cuda.synchronize()
+            P.set_spmm_timer(None)
         if dist_mode:
             elapsed = _allreduce(elapsed, dev, torch.distributed.ReduceOp.MAX)
         final_loss = float(loss)
@@ -826,7 +907,7 @@ def main():
                     timer_steps=timer_steps, events_in_loop=events_in_loop, elapsed=elapsed,
                     final_loss=final_loss, counts=counts, gathered_step=gathered_step,
                     visited_step=visited_step, dense_ms=dense_ms,
-                    frontier_on=bool(trainer.frontier),
+                    frontier_on=bool(trainer.frontier), outputs=outputs,
                     value=gathered_step * args.steps / elapsed,
                     ms_per_step=1000.0 * elapsed / args.steps)
 
@@ -997,6 +1078,8 @@ def main():
         if dist_mode:
             torch.distributed.destroy_process_group()
         return
+    if args.dump_outputs:
+        write_outputs(args.dump_outputs, res["outputs"])
     cpu = None
     if not args.no_cpu_baseline and not dist_mode and not sharded_gen:
         log("[bench] timing the reference CPU path (bounded sample) ...")
@@ -1181,6 +1264,12 @@ def main():
         "step_summary": step_summary(1000.0 * elapsed / args.steps, dense_ms, torch_ref, dropin,
                                      dropin_fused, dropin_bwd),
     }
+    out["full"] = args.full
+    if not args.full:   # not measured in a plain run: left out of the line
+        for k in FULL_ONLY_KEYS:
+            del out[k]
+        out["frontier"] = {"enabled": frontier_on}
+        out["step_summary"] = {"ms_per_step": out["step_summary"]["ms_per_step"]}
     print(json.dumps(out), file=out_stream, flush=True)
     if dist_mode:
         torch.distributed.destroy_process_group()

@@ -15,7 +15,8 @@ def test_bench_help_lists_the_contract_flags():
                        capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     for flag in ("--gpus", "--steps", "--warmup", "--config", "--vertex-order",
-                 "--exchange-parts", "--frontier-parts", "--scaling", "--dense-check"):
+                 "--exchange-parts", "--frontier-parts", "--scaling", "--dense-check",
+                 "--full", "--dump-outputs"):
         assert flag in r.stdout + r.stderr, flag
 
 

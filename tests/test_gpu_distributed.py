@@ -221,8 +221,9 @@ def test_bench_two_ranks_on_c2(tmp_path, partition):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
            "--standalone", "--local-addr=127.0.0.1",
            os.path.join(ROOT, "bench.py"), "--gpus", "2", "--config", "C2", "--steps", "3",
-           "--warmup", "1", "--dense-check", "1", "--frontier", "on", "--partition", partition,
-           "--weak-beside", "2", "--partition-beside", "0", "--chain-beside", "0"] + \
+           "--warmup", "1", "--full", "--dense-check", "1", "--frontier", "on",
+           "--partition", partition, "--weak-beside", "2", "--partition-beside", "0",
+           "--chain-beside", "0"] + \
         (["--column-chains", "2"] if chains else [])
     env = dict(os.environ, OMP_NUM_THREADS="4", BBGR_DIST_BACKEND="gloo")
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
@@ -248,7 +249,7 @@ def test_bench_two_ranks_survives_a_failed_beside_run(tmp_path):
            "--standalone", "--local-addr=127.0.0.1",
            os.path.join(ROOT, "bench.py"), "--gpus", "2", "--config", "C2", "--steps", "2",
            "--warmup", "1", "--dense-check", "0", "--frontier", "on", "--weak-beside", "0",
-           "--partition", "columns"]
+           "--partition", "columns", "--full"]
     env = dict(os.environ, OMP_NUM_THREADS="4", BBGR_DIST_BACKEND="gloo",
                BBGR_BENCH_FAIL_BESIDE="users")
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
@@ -268,7 +269,7 @@ def test_bench_two_ranks_survives_a_failed_main_run(tmp_path):
            "--standalone", "--local-addr=127.0.0.1",
            os.path.join(ROOT, "bench.py"), "--gpus", "2", "--config", "C2", "--steps", "2",
            "--warmup", "1", "--dense-check", "0", "--frontier", "on", "--weak-beside", "0",
-           "--partition", "users"]
+           "--partition", "users", "--full"]
     env = dict(os.environ, OMP_NUM_THREADS="4", BBGR_DIST_BACKEND="gloo",
                BBGR_BENCH_FAIL_BESIDE="main")
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
@@ -304,7 +305,8 @@ def test_bench_two_ranks_measures_both_partitions(tmp_path):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
            "--standalone", "--local-addr=127.0.0.1",
            os.path.join(ROOT, "bench.py"), "--gpus", "2", "--config", "C2", "--steps", "3",
-           "--warmup", "1", "--dense-check", "1", "--frontier", "on", "--weak-beside", "0"]
+           "--warmup", "1", "--dense-check", "1", "--frontier", "on", "--weak-beside", "0",
+           "--full"]
     env = dict(os.environ, OMP_NUM_THREADS="4", BBGR_DIST_BACKEND="gloo")
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]

@@ -31,9 +31,9 @@ def test_abi_version_and_error_text():
     assert isinstance(L.bbgr_last_error(), bytes)
 
 
-def _c_sizeof(struct_name: str) -> int:
+def _c_sizeof(struct_name: str, out_dir) -> int:
     src = f'#include "bbgr.h"\n#include <stdio.h>\nint main(){{printf("%zu", sizeof({struct_name}));}}'
-    exe = "/tmp/bbgr_sizeof_" + struct_name
+    exe = str(out_dir / ("bbgr_sizeof_" + struct_name))   # the test's own directory
     subprocess.run(["gcc", "-x", "c", "-", "-I", str(_lib.HEADER_PATH.parent), "-o", exe],
                    input=src, text=True, check=True)
     return int(subprocess.run([exe], capture_output=True, text=True, check=True).stdout)
@@ -43,8 +43,8 @@ def _c_sizeof(struct_name: str) -> int:
                                         ("bbgr_spmm_args", _lib.SpmmArgs),
                                         ("bbgr_bpr_args", _lib.BprArgs),
                                         ("bbgr_eval_args", _lib.EvalArgs)])
-def test_struct_layout_matches_header(cname, pyty):
-    assert _c_sizeof(cname) == ctypes.sizeof(pyty)
+def test_struct_layout_matches_header(cname, pyty, tmp_path):
+    assert _c_sizeof(cname, tmp_path) == ctypes.sizeof(pyty)
 
 
 def test_invalid_arguments_rejected_without_gpu():

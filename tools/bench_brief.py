@@ -8,7 +8,8 @@ import sys
 
 def main(path: str):
     j = json.loads(open(path).read().strip().splitlines()[-1])
-    r = j["roofline"]
+    nan = float("nan")   # a plain run (no --full) has no roofline figures
+    r = j.get("roofline") or {"frac": nan, "avg_launch_ms": nan}
     print(f"ms/step {j['ms_per_step']:.3f}  value {j['value'] / 1e9:.2f} G/s  frac {r['frac']:.3f}"
           f"  dom {r['avg_launch_ms']:.4f} ms  dense {j.get('dense_ms_per_step')}"
           f"  part {j.get('partition')}  loss {j.get('final_loss')}")

@@ -11,8 +11,8 @@
 #   box        GPU / driver / partition / clock facts of this box (box.txt)
 #   tests      the whole `pytest -m gpu` suite (TESTS="<files / -k ...>" narrows it)
 #   smoke      __graft_entry__.smoke()
-#   bench      the default bench line (BENCH_ARGS appended), bench.json
-#   quick      bench --steps 10 without the CPU / stock-torch / drop-in legs
+#   bench      the default bench line with --full (BENCH_ARGS appended), bench.json
+#   quick      bench --full --steps 10 without the CPU / stock-torch / drop-in legs
 #   profile    tools/profile_box.sh <tag> (kernel trace + FETCH_SIZE + WRITE_SIZE)
 #   storeab    output store policy A/B (BBGR_STREAM_OUT = split / nt / none):
 #              a quick bench and a WRITE_SIZE + FETCH_SIZE pass over the SpMM
@@ -38,7 +38,7 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
 hard() {  # rc, step, log: stop on a fault / abort / segfault / time limit
   case $1 in 124|134|137|139) echo "HARD FAIL ($1) in $2"; tail -30 "$3"; exit 1;; esac
 }
-quick_args="--steps 10 --warmup 2 --no-cpu-baseline --no-torch-reference --dense-check 0"
+quick_args="--full --steps 10 --warmup 2 --no-cpu-baseline --no-torch-reference --dense-check 0"
 
 for step in "$@"; do
   s0=$(date +%s)
@@ -62,7 +62,7 @@ for step in "$@"; do
       rc=$?; hard $rc smoke "$O/smoke.log"; echo "SMOKE rc=$rc"; tail -1 "$O/smoke.log"
       [ $rc -eq 0 ] || exit 1 ;;
     bench)
-      timeout -k 10 900 python -u bench.py ${BENCH_ARGS:-} > "$O/bench.json" 2> "$O/bench.log"
+      timeout -k 10 900 python -u bench.py --full ${BENCH_ARGS:-} > "$O/bench.json" 2> "$O/bench.log"
       rc=$?; hard $rc bench "$O/bench.log"; echo "BENCH rc=$rc"
       [ $rc -eq 0 ] || { tail -20 "$O/bench.log"; exit 1; }
       python tools/bench_brief.py "$O/bench.json" ;;
@@ -122,7 +122,7 @@ for step in "$@"; do
       n=${N:-2}
       BBGR_DIST_BACKEND=gloo timeout -k 10 1000 python -m torch.distributed.run --nnodes=1 \
         --nproc-per-node "$n" --master-addr 127.0.0.1 --master-port 29611 bench.py --gpus "$n" \
-        --steps 3 --warmup 1 ${REHEARSE_ARGS:-} > "$O/rehearsal_gloo$n.json" 2> "$O/rehearsal_gloo$n.log"
+        --full --steps 3 --warmup 1 ${REHEARSE_ARGS:-} > "$O/rehearsal_gloo$n.json" 2> "$O/rehearsal_gloo$n.log"
       rc=$?; hard $rc rehearse "$O/rehearsal_gloo$n.log"; echo "REHEARSE N=$n rc=$rc"
       [ $rc -eq 0 ] || { tail -20 "$O/rehearsal_gloo$n.log"; exit 1; }
       python tools/bench_brief.py "$O/rehearsal_gloo$n.json" ;;
@@ -146,7 +146,7 @@ for step in "$@"; do
         extra=""
         case $c in C1) extra="--variant plain";; C3) extra="--variant cu_fair --no-torch-reference";;
                    C5) extra="--no-torch-reference --steps 5 --warmup 1";; esac
-        timeout -k 10 900 python -u bench.py --config $c $extra > "$O/${c,,}_bench.json" \
+        timeout -k 10 900 python -u bench.py --full --config $c $extra > "$O/${c,,}_bench.json" \
           2> "$O/${c,,}_bench.log"
         rc=$?; hard $rc "bench $c" "$O/${c,,}_bench.log"
         [ $rc -eq 0 ] || { tail -20 "$O/${c,,}_bench.log"; exit 1; }
