@@ -695,10 +695,12 @@ __global__ __launch_bounds__(256) void ego_rows_kernel(long B, const long *iu, c
                                                        float reg, int *counts, float *g_u,
                                                        long ldgu, float *g_i, long ldgi,
                                                        float scale, int *counts_u_out) {
-  constexpr int V = D / 64;
+  // D < 64: one float4 per lane, lanes < D / 4 of the slot's group active
+  constexpr int V = D >= 64 ? D / 64 : 1;
   const long s = (long)blockIdx.x * 16 + (threadIdx.x >> 4);
   const int lane = threadIdx.x & 15;
   if (s >= 3 * B) return;
+  if (D < 64 && lane >= D / 4) return;
   const int n = counts[s];
   const bool user = s < B;
   if (user && counts_u_out && lane == 0) counts_u_out[s] = n;
@@ -1463,8 +1465,8 @@ extern "C" int bbgr_ego_rows(int64_t B, int32_t d, const int64_t *cu, const int6
                              int64_t ldgu, float *g_i, int64_t ldgi, float scale,
                              int32_t *counts_u_out, bbgr_stream_t stream) {
   BBGR_REQUIRE(B >= 0 && 3 * B < (1LL << 31), "bbgr_ego_rows: bad batch");
-  if (d != 64 && d != 128 && d != 256) {
-    set_error("bbgr_ego_rows: embedding dim %d unsupported (64, 128, 256)", d);
+  if (!supported_width(d)) {
+    set_error("bbgr_ego_rows: embedding dim %d unsupported (8, 16, 32, 64, 128, 256)", d);
     return BBGR_ERR_UNSUPPORTED;
   }
   if (B == 0) return BBGR_OK;
@@ -1484,6 +1486,9 @@ extern "C" int bbgr_ego_rows(int64_t B, int32_t d, const int64_t *cu, const int6
                      (const long *)ii, ue, (long)ldue, ie, (long)ldie, dloss, inv_b, reg,   \
                      counts, g_u, (long)ldgu, g_i, (long)ldgi, scale, counts_u_out)
   switch (d) {
+    case 8: BBGR_EGO_ROWS(8); break;
+    case 16: BBGR_EGO_ROWS(16); break;
+    case 32: BBGR_EGO_ROWS(32); break;
     case 64: BBGR_EGO_ROWS(64); break;
     case 128: BBGR_EGO_ROWS(128); break;
     default: BBGR_EGO_ROWS(256); break;

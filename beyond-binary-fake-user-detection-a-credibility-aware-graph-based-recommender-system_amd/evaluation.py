@@ -38,6 +38,10 @@ from .graph import Csr
 from .sampler import nonempty_rows
 
 NOUT = 11   # per K: p, r, ndcg, logpop, selfinfo, high_r, low_r, high_n, low_n, n, covered
+# embedding widths below the kernels' smallest (bbgr_eval_sampled: 64, 128, 256;
+# bbgr_eval_full: 64, 128) that the propagation supports: evaluated zero-padded
+NARROW_WIDTHS = (8, 16, 32)
+EVAL_MIN_WIDTH = 64
 
 
 def make_cred_groups(users: np.ndarray, cred: np.ndarray, pct: float):
@@ -117,9 +121,25 @@ def cred_groups(users: torch.Tensor, cred: torch.Tensor, pct: float) -> torch.Te
     return flags
 
 
+def _pad_narrow(t: torch.Tensor) -> torch.Tensor:
+    """A [n, d] table of a narrow width as [n, 64] for the evaluation kernels,
+    which start at 64 columns (one eval-time copy): columns [0, d/2) stay,
+    columns [d/2, d) move to 32 + [0, d/2), the rest is zero. Zero columns add
+    exact zeros to every dot product, and bbgr_eval_full's fma chain (components
+    0, D/2, 1, D/2 + 1, ...) then runs through the d columns in the order it
+    would at width d before the zeros, so its scores are that chain's bits."""
+    h, H = t.shape[1] // 2, EVAL_MIN_WIDTH // 2
+    out = t.new_zeros(t.shape[0], EVAL_MIN_WIDTH)
+    out[:, :h] = t[:, :h]
+    out[:, H:H + h] = t[:, h:]
+    return out
+
+
 def _tables(user_emb, item_emb, item_pop, cred, dev):
     uf = user_emb.detach().to(torch.float32).contiguous()
     itf = item_emb.detach().to(torch.float32).contiguous()
+    if uf.dim() == 2 and uf.shape[1] == itf.shape[1] and uf.shape[1] in NARROW_WIDTHS:
+        uf, itf = _pad_narrow(uf), _pad_narrow(itf)
     pop = torch.as_tensor(np.asarray(item_pop, np.float32) if not isinstance(item_pop, torch.Tensor)
                           else item_pop).to(dev, torch.float32).contiguous()
     cred_t = torch.as_tensor(np.asarray(cred, np.float32) if not isinstance(cred, torch.Tensor)

@@ -566,6 +566,8 @@ int bbgr_ego_slots(int64_t B, const int64_t *users, const int64_t *pos, const in
 /* sum itself; the in-backward Adam's (K+1) * ego rows without a mul launch). */
 /* counts_u_out (nullable, int32 [B]): slot s < B's user count n (0 off the   */
 /* first slots), for bbgr_rows_add_slots over the same cu.                    */
+/* d in {8, 16, 32, 64, 128, 256}; any other width returns                    */
+/* BBGR_ERR_UNSUPPORTED before a launch.                                      */
 int bbgr_ego_rows(int64_t B, int32_t d, const int64_t *cu, const int64_t *sp, const int64_t *sn,
                   const int64_t *iu, const int64_t *ii, const float *ue, int64_t ldue,
                   const float *ie, int64_t ldie, const float *dloss, float reg, int32_t *counts,

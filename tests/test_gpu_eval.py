@@ -29,7 +29,7 @@ def _split(U, I, E, seed):
     return e[:, ~test], e[:, test]
 
 
-@pytest.mark.parametrize("d", [64, 128])
+@pytest.mark.parametrize("d", [64, 128, 256])
 def test_eval_sampled_vs_oracle(d):
     from bbgr.evaluation import evaluate_sampled
     U, I = 2000, 1500

@@ -559,7 +559,9 @@ def test_fused_trainer_step_vs_oracle(gold, variant):
 
 
 @pytest.mark.parametrize("K,d,frontier", [(0, 64, True), (1, 64, True), (4, 64, True),
-                                         (2, 128, True), (3, 256, True), (3, 128, False)])
+                                         (2, 128, True), (3, 256, True), (3, 128, False),
+                                         (3, 8, True), (2, 16, True), (3, 32, True),
+                                         (3, 32, False)])
 def test_fused_trainer_shapes_vs_oracle(K, d, frontier):
     """The GS training step (fused Adam, frontier masks) at other depths and
     widths: loss at 1e-5 and the Adam update normwise vs the float64 oracle."""
@@ -866,7 +868,9 @@ def test_first_slot_kernel_is_the_first_occurrence(n, hi):
 
 
 @pytest.mark.parametrize("B,U,I,d", [(1, 3, 2, 64), (8192, 50_000, 20_000, 64), (4096, 50, 30, 64),
-                                     (300, 300, 7, 128), (512, 900, 40, 256)])
+                                     (300, 300, 7, 128), (512, 900, 40, 256),
+                                     (300, 300, 7, 8), (300, 300, 7, 16), (300, 300, 7, 32),
+                                     (512, 900, 40, 8), (512, 900, 40, 16), (512, 900, 40, 32)])
 def test_ego_rows_kernel_is_the_atomic_formulation(B, U, I, d):
     """bbgr_ego_rows (first-slot counts, then each slot's y added n times from
     +0.0) is bitwise the bbgr_bpr ego rows it replaced (float atomics of the
@@ -915,7 +919,10 @@ def test_ego_rows_kernel_is_the_atomic_formulation(B, U, I, d):
 
 @pytest.mark.parametrize("B,U,d,invalid_first", [(1, 3, 64, False), (8192, 5_000_000, 64, False),
                                                  (8192, 50_000, 64, True), (4096, 50, 128, True),
-                                                 (300, 300, 256, True), (513, 7, 64, False)])
+                                                 (300, 300, 256, True), (513, 7, 64, False),
+                                                 (300, 300, 8, True), (300, 300, 16, True),
+                                                 (300, 300, 32, True), (512, 900, 8, False),
+                                                 (512, 900, 16, False), (512, 900, 32, False)])
 def test_rows_add_slots_is_the_sorted_scatter(B, U, d, invalid_first):
     """bbgr_rows_add_slots (first slots and counts from bbgr_ego_slots /
     bbgr_ego_rows' counts_u_out) is bitwise bbgr_scatter_add_rows over the
