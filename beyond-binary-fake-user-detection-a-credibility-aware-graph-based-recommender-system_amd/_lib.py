@@ -80,8 +80,8 @@ class SpmmArgs(ctypes.Structure):
         ("use_range", c_int32),
         ("range", c_int32 * 6),
         ("adam_param", c_void_p), ("adam_exp_avg", c_void_p), ("adam_exp_avg_sq", c_void_p),
-        ("adam_ld", c_int64), ("adam_lr", c_float), ("adam_beta1", c_float),
-        ("adam_beta2", c_float), ("adam_eps", c_float), ("adam_weight_decay", c_float),
+        ("adam_ld", c_int64), ("adam_lr", c_float), ("adam_beta1", c_double),
+        ("adam_beta2", c_double), ("adam_eps", c_float), ("adam_weight_decay", c_float),
         ("adam_bias_correction1", c_float), ("adam_bias_correction2_sqrt", c_float),
         ("stream_from", c_int32), ("stream_out_from", c_int32),
         ("adam_bc_table", c_void_p), ("adam_state", c_void_p),
@@ -200,9 +200,9 @@ _SIGNATURES = {
     "bbgr_epilogue": ([c_int32, _P, c_int64, ctypes.POINTER(SpmmArgs), _P], c_int32),
     "bbgr_bpr": ([ctypes.POINTER(BprArgs), _P], c_int32),
     "bbgr_bpr_reduce": ([c_int64, _P, c_float, c_float, _P, _P], c_int32),
-    "bbgr_adam": ([c_int64, _P, _P, _P, _P, c_float, c_float, c_float, c_float,
+    "bbgr_adam": ([c_int64, _P, _P, _P, _P, c_float, c_double, c_double, c_float,
                    c_float, c_float, c_float, c_float, _P], c_int32),
-    "bbgr_adam_dev": ([c_int64, _P, _P, _P, _P, c_float, c_float, c_float, c_float,
+    "bbgr_adam_dev": ([c_int64, _P, _P, _P, _P, c_float, c_double, c_double, c_float,
                        c_float, c_float, _P, _P, _P], c_int32),
     "bbgr_step_begin": ([_P, _P], c_int32),
     "bbgr_mark_rows": ([c_int64, _P, ctypes.c_uint8, _P, c_int64, _P], c_int32),
@@ -299,7 +299,7 @@ def lib() -> ctypes.CDLL:
             fn = getattr(handle, name)
             fn.argtypes = argtypes
             fn.restype = restype
-        if handle.bbgr_abi_version() != 11:
+        if handle.bbgr_abi_version() != 12:
             raise ImportError("libbbgr.so ABI version mismatch")
         _lib = handle
     return _lib

@@ -127,9 +127,13 @@ struct AdamConsts {
   float bc2s;   // sqrt(bias_correction2)
 };
 
-__host__ __device__ inline AdamConsts adam_consts(float lr, float b1, float b2, float eps,
+// The betas arrive as the caller's doubles: torch forms 1 - beta in double and
+// rounds once. 1.0f - (float)beta carries beta's own rounding, up to 2^-25
+// against a difference of 1 - beta: measured over 12 steps, 1.3e-5 of
+// exp_avg_sq at beta2 = 0.999 and 1.4e-3 at 0.99999 (tests/test_gpu_adam.py).
+__host__ __device__ inline AdamConsts adam_consts(float lr, double b1, double b2, float eps,
                                                   float wd, float bc1, float bc2s) {
-  return AdamConsts{lr / bc1, 1.0f - b1, b2, 1.0f - b2, eps, wd, bc2s};
+  return AdamConsts{lr / bc1, (float)(1.0 - b1), (float)b2, (float)(1.0 - b2), eps, wd, bc2s};
 }
 
 __device__ __forceinline__ void adam_elem(float &p, float g, float &m, float &v,

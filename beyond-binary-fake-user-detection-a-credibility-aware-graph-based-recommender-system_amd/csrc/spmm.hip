@@ -1590,6 +1590,8 @@ extern "C" int bbgr_bpr_fwd_bwd(const bbgr_bpr_args *args, bbgr_stream_t stream)
   return bbgr_bpr(args, stream);
 }
 
+// The sketch's float betas: 1 - beta is formed from the rounded beta here
+// (bbgr_adam takes the caller's doubles).
 extern "C" int bbgr_adam_f32(int64_t n, float *param, const float *grad, float *exp_avg,
                              float *exp_avg_sq, float lr, float beta1, float beta2, float eps,
                              float weight_decay, float grad_scale, float bias_correction1,

@@ -191,7 +191,9 @@ static float *workspace(const Product &pr, int d, const at::Device &dev) {
 // corrections): bbgr.optim.FusedAdam in backward mode hands these over.
 struct AdamTable {
   Tensor p, m, v;
-  float lr = 1e-3f, beta1 = 0.9f, beta2 = 0.999f, eps = 1e-8f, wd = 0.f;
+  float lr = 1e-3f;
+  double beta1 = 0.9, beta2 = 0.999;   // doubles: 1 - beta is formed in double (adam_consts)
+  float eps = 1e-8f, wd = 0.f;
   float bc1 = 1.f, bc2s = 1.f;
   bool moments_graph = false;   // m, v in the graph's row order (adam_moments_unmapped)
   // p is then graph-ordered too (the optimizer's master copy) and every updated
@@ -1541,9 +1543,9 @@ static void bpr_adam_backward_cuda(const Tensor &dloss, const Tensor &uf_, const
   StepAdam sa;
   sa.user_slot = uslots[0];
   sa.user_count = uslots[1];
-  sa.user = AdamTable{u0, m_u, v_u, (float)lr, (float)beta1, (float)beta2, (float)eps, (float)wd,
+  sa.user = AdamTable{u0, m_u, v_u, (float)lr, beta1, beta2, (float)eps, (float)wd,
                       (float)bc1_u, (float)bc2s_u};
-  sa.item = AdamTable{i0, m_i, v_i, (float)lr, (float)beta1, (float)beta2, (float)eps, (float)wd,
+  sa.item = AdamTable{i0, m_i, v_i, (float)lr, beta1, beta2, (float)eps, (float)wd,
                       (float)bc1_i, (float)bc2s_i};
   // moments in the graph's row order: only the caller-order weight rows are
   // read and written through the row maps (an input-order pair; otherwise the

@@ -1103,7 +1103,7 @@ extern "C" int bbgr_bpr_reduce(int64_t batch, const float *parts, float reg,
 }
 
 static int adam_launch(int64_t n, float *param, const float *grad, float *exp_avg,
-                       float *exp_avg_sq, float lr, float beta1, float beta2, float eps,
+                       float *exp_avg_sq, float lr, double beta1, double beta2, float eps,
                        float weight_decay, float grad_scale, float bias_correction1,
                        float bias_correction2_sqrt, const float *bc, const long *state,
                        hipStream_t st) {
@@ -1131,8 +1131,8 @@ static int adam_launch(int64_t n, float *param, const float *grad, float *exp_av
 }
 
 extern "C" int bbgr_adam(int64_t n, float *param, const float *grad,
-                         float *exp_avg, float *exp_avg_sq, float lr, float beta1,
-                         float beta2, float eps, float weight_decay, float grad_scale,
+                         float *exp_avg, float *exp_avg_sq, float lr, double beta1,
+                         double beta2, float eps, float weight_decay, float grad_scale,
                          float bias_correction1, float bias_correction2_sqrt,
                          bbgr_stream_t stream) {
   BBGR_REQUIRE(n >= 0, "bbgr_adam: negative n");
@@ -1144,7 +1144,7 @@ extern "C" int bbgr_adam(int64_t n, float *param, const float *grad,
 }
 
 extern "C" int bbgr_adam_dev(int64_t n, float *param, const float *grad, float *exp_avg,
-                             float *exp_avg_sq, float lr, float beta1, float beta2,
+                             float *exp_avg_sq, float lr, double beta1, double beta2,
                              float eps, float weight_decay, float grad_scale,
                              const float *bc_table, const int64_t *state,
                              bbgr_stream_t stream) {

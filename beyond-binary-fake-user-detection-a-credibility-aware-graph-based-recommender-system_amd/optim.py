@@ -4,7 +4,10 @@ Drop-in for ``torch.optim.Adam(model.parameters(), lr=cfg.lr)``
 (Version-2/lighgcn_cu_pop.py:793, step at :863): same defaults
 (betas=(0.9, 0.999), eps=1e-8, weight_decay=0), same state keys
 (``step``, ``exp_avg``, ``exp_avg_sq``) so state_dicts interchange.
-Bias corrections are computed on the host in double, as torch does.
+Bias corrections and 1 - beta are computed on the host in double, as torch
+does (the betas cross the C ABI as doubles). tests/test_gpu_adam.py holds every
+path to a float64 trajectory over several steps, with non-default
+hyper-parameters, and moves state_dicts between this class and torch's.
 """
 from __future__ import annotations
 

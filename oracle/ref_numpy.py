@@ -356,9 +356,25 @@ def bpr_loss(uf, itf, ue, ie, users, pos, neg, reg, pop=None, lambda_fair=0.0):
                                              np.asarray(pop, np.float64)[pos] * sp_], 1))
 
 
-def adam_step(p, g, m, v, step, lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8):
-    """torch.optim.Adam (amsgrad=False, weight_decay=0) in float64."""
+# (lr, beta1, beta2, eps, weight_decay): the hyper-parameter rows the Adam tests
+# sweep (tests/test_oracle.py on the CPU, tests/test_gpu_adam.py on every HIP path)
+ADAM_ROWS = (
+    (1e-3, 0.9, 0.999, 1e-8, 0.0),
+    (1e-3, 0.8, 0.99, 1e-8, 0.0),
+    (1e-3, 0.9, 0.9999, 1e-8, 0.0),
+    (1e-3, 0.9, 0.99999, 1e-8, 0.0),
+    (1e-3, 0.9, 0.999, 1e-8, 1e-2),
+    (1e-2, 0.5, 0.9, 1e-3, 1e-1),
+    (1e-3, 0.0, 0.999, 1e-8, 0.0),
+)
+
+
+def adam_step(p, g, m, v, step, lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0):
+    """torch.optim.Adam (amsgrad=False) in float64; weight_decay is torch's L2
+    form (g += weight_decay * p before the moments)."""
     p, g, m, v = (np.asarray(a, np.float64).copy() for a in (p, g, m, v))
+    if weight_decay != 0.0:
+        g = g + weight_decay * p
     m = m + (1 - beta1) * (g - m)
     v = beta2 * v + (1 - beta2) * g * g
     bc1 = 1 - beta1 ** step

@@ -74,13 +74,13 @@ int main(void) {
   expect_error("epilogue null args", bbgr_epilogue(4, f4, 64, NULL, NULL));
   expect_error("epilogue negative rows", bbgr_epilogue(-1, f4, 64, &a, NULL));
   expect_error("bpr null", bbgr_bpr(NULL, NULL));
-  expect_error("adam negative n", bbgr_adam(-1, f4, f4, f4, f4, 1e-3f, 0.9f, 0.999f, 1e-8f,
+  expect_error("adam negative n", bbgr_adam(-1, f4, f4, f4, f4, 1e-3f, 0.9, 0.999, 1e-8f,
                                             0.f, 1.f, 0.1f, 0.03f, NULL));
-  expect_error("adam null tensor", bbgr_adam(4, NULL, f4, f4, f4, 1e-3f, 0.9f, 0.999f, 1e-8f,
+  expect_error("adam null tensor", bbgr_adam(4, NULL, f4, f4, f4, 1e-3f, 0.9, 0.999, 1e-8f,
                                              0.f, 1.f, 0.1f, 0.03f, NULL));
-  expect_ok("adam empty", bbgr_adam(0, NULL, NULL, NULL, NULL, 1e-3f, 0.9f, 0.999f, 1e-8f,
+  expect_ok("adam empty", bbgr_adam(0, NULL, NULL, NULL, NULL, 1e-3f, 0.9, 0.999, 1e-8f,
                                     0.f, 1.f, 0.1f, 0.03f, NULL));
-  expect_error("adam_dev null state", bbgr_adam_dev(4, f4, f4, f4, f4, 1e-3f, 0.9f, 0.999f,
+  expect_error("adam_dev null state", bbgr_adam_dev(4, f4, f4, f4, f4, 1e-3f, 0.9, 0.999,
                                                     1e-8f, 0.f, 1.f, f4, NULL, NULL));
   expect_error("step_begin null", bbgr_step_begin(NULL, NULL));
   expect_error("sample bad sizes", bbgr_sample(1, NULL, NULL, NULL, 0, NULL, 0.f, 5, 1, 0,

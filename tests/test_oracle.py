@@ -200,6 +200,45 @@ def test_adam_matches_torch():
     assert nrel(tp.detach().numpy(), p) < 1e-12
 
 
+def test_kat_adam_two_steps_with_weight_decay():
+    """One scalar, lr .1, betas (.5, .75), eps .5, weight_decay .5, by hand:
+    t=1: g = 1 + .5*1 = 1.5; m = .75; v = .25*2.25 = .5625; bc1 = .5, sqrt(bc2) = .5;
+         denom = .75/.5 + .5 = 2; p = 1 - (.1/.5)*.75/2 = .925
+    t=2: g = 0 + .5*.925 = .4625; m = .75 + .5*(.4625 - .75) = .60625;
+         v = .75*.5625 + .25*.4625^2 = .4753515625; bc1 = .75, bc2 = .4375;
+         p = .925 - (.1/.75)*.60625/(sqrt(.4753515625/.4375) + .5)"""
+    kw = dict(lr=0.1, beta1=0.5, beta2=0.75, eps=0.5, weight_decay=0.5)
+    p, m, v = R.adam_step([1.0], [1.0], [0.0], [0.0], 1, **kw)
+    assert abs(p[0] - 0.925) < 1e-15 and m[0] == 0.75 and v[0] == 0.5625
+    p, m, v = R.adam_step(p, [0.0], m, v, 2, **kw)
+    assert abs(m[0] - 0.60625) < 1e-15 and abs(v[0] - 0.4753515625) < 1e-15
+    want = 0.925 - (0.1 / 0.75) * 0.60625 / (math.sqrt(0.4753515625 / 0.4375) + 0.5)
+    assert abs(p[0] - want) < 1e-15 and abs(want - 0.8725911942358845) < 1e-15
+
+
+@pytest.mark.parametrize("row", R.ADAM_ROWS)
+def test_adam_matches_torch_float64_over_steps(row):
+    """Six steps of every hyper-parameter row against torch.optim.Adam on
+    float64 CPU tensors (an independent high-precision restatement); half the
+    rows idle each step, so zero gradients meet non-zero moments."""
+    lr, b1, b2, eps, wd = row
+    rng = np.random.default_rng(9)
+    p0 = rng.normal(size=(24, 8))
+    tp = torch.nn.Parameter(torch.tensor(p0))
+    opt = torch.optim.Adam([tp], lr=lr, betas=(b1, b2), eps=eps, weight_decay=wd)
+    p, m, v = p0.copy(), np.zeros_like(p0), np.zeros_like(p0)
+    for step in range(1, 7):
+        g = rng.normal(size=p0.shape) * 10.0 ** rng.uniform(-6, -2, size=(24, 1))
+        g[rng.permutation(24)[:12]] = 0.0
+        tp.grad = torch.tensor(g)
+        opt.step()
+        p, m, v = R.adam_step(p, g, m, v, step, lr, b1, b2, eps, wd)
+    st = opt.state[tp]
+    assert nrel(tp.detach().numpy() - p0, p - p0) < 1e-12
+    assert nrel(st["exp_avg"].numpy(), m) < 1e-12
+    assert nrel(st["exp_avg_sq"].numpy(), v) < 1e-12
+
+
 @pytest.mark.parametrize("betas", [(0.9, 0.999), (0.8, 0.99), (0.9, 0.9999)])
 def test_bias_correction_table_is_exact_past_its_end(betas):
     """The device step state's kernels clamp t to the table end:
