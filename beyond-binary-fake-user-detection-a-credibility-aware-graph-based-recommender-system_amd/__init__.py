@@ -10,6 +10,7 @@ behind the reference's own module API:
   bbgr.lightgcn          lightgcn.py / lightgcn-1.py   (symmetric A_hat)
   bbgr.trainer           fused native training step (sampler + fwd + BPR + bwd + Adam)
   bbgr.distributed       user-row sharded training over RCCL
+  bbgr.recommend         top-k recommendation lists, full-ranking metrics from lists
   bbgr.sampler, bbgr.optim, bbgr.bpr, bbgr.propagate, bbgr.graph
 
 All device compute goes through libbbgr.so (C ABI: include/bbgr.h).

@@ -134,6 +134,17 @@ class EvalArgs(ctypes.Structure):
     ]
 
 
+class RecommendArgs(ctypes.Structure):
+    """bbgr_recommend_args (bbgr_recommend)."""
+    _fields_ = [
+        ("n_users", c_int64), ("users", c_void_p), ("n_user_rows", c_int64),
+        ("uf", c_void_p), ("lduf", c_int64), ("itf", c_void_p), ("ldif", c_int64),
+        ("d", c_int32), ("n_items", c_int32), ("k", c_int32),
+        ("ex_indptr", c_void_p), ("ex_indices", c_void_p), ("item_mask", c_void_p),
+        ("topk", c_void_p), ("topk_score", c_void_p),
+    ]
+
+
 class Pcg64State(ctypes.Structure):
     """bbgr_pcg64: numpy's PCG64 bit_generator.state (128-bit state and
     increment as two 64-bit halves, the buffered 32-bit output)."""
@@ -247,6 +258,9 @@ _SIGNATURES = {
     "bbgr_eval_sampled": ([ctypes.POINTER(EvalArgs), _P, ctypes.POINTER(c_size_t), _P],
                           c_int32),
     "bbgr_eval_full": ([ctypes.POINTER(EvalArgs), _P, ctypes.POINTER(c_size_t), _P], c_int32),
+    "bbgr_eval_lists": ([ctypes.POINTER(EvalArgs), _P, ctypes.POINTER(c_size_t), _P], c_int32),
+    "bbgr_recommend": ([ctypes.POINTER(RecommendArgs), _P, ctypes.POINTER(c_size_t), _P],
+                       c_int32),
     "bbgr_eval_draw_candidates": ([ctypes.POINTER(Pcg64State), c_int64, _P, _P, _P, _P, _P,
                                    c_int64, c_int32, _P], c_int32),
     "bbgr_nonempty_rows": ([c_int32, _P, _P, _P, _P, ctypes.POINTER(c_size_t), _P],

@@ -30,31 +30,21 @@
 #include <vector>
 
 #include "common.h"
+#include "topk.h"
 
 namespace bbgr {
 
 constexpr int EVAL_MAX_CAND = 256;   // 1 + n_neg
 constexpr int EVAL_MAX_K = 64;       // sampled k_max
 constexpr int EVAL_FULL_MAX_K = 32;  // full-ranking k_max
+constexpr int EVAL_LISTS_MAX_K = 128;  // caller-supplied lists (bbgr_eval_lists)
 constexpr int EVAL_NTERM = 10;       // p, r, ndcg, logpop, selfinfo, high_r, low_r, high_n, low_n, n
 constexpr int EVAL_NOUT = 11;        // + covered count
 constexpr int EVAL_CHUNK = 4096;     // users per eval_terms workgroup (256 threads x 16)
 constexpr int ROW_CACHE = 64;        // LDS copy of test / train rows up to this length
 constexpr int FULL_THREADS = 512;    // 8 waves: 2 per SIMD hide the check path
 constexpr int FULL_USERS = 256;      // users per full-ranking workgroup (8 waves x 32)
-constexpr int FULL_TILE = 128;       // items per full-ranking LDS tile
-constexpr long FULL_BATCH = 1l << 18;  // users per full-ranking launch
 constexpr float TRAIN_MASK = -1e9f;  // Version-2:703 scores[train_items] = -1e9
-
-__device__ __forceinline__ int lower_bound_i32(const int *a, int n, int x) {
-  int lo = 0, hi = n;
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (a[mid] < x) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
-}
 
 __device__ __forceinline__ bool sorted_has(const int *a, int n, int x) {
   const int lo = lower_bound_i32(a, n, x);
@@ -199,8 +189,6 @@ __global__ __launch_bounds__(256) void eval_sampled_kernel(EvalParams P) {
 // ===========================================================================
 // Full-ranking protocol
 // ===========================================================================
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 struct FullParams {
   long n_users;               // users in this launch
   const long *users;
@@ -213,21 +201,6 @@ struct FullParams {
   float *list_score;          // [n_users][n_splits][2][KM]
   int *list_item;
 };
-
-// One (score, item) into a sorted register list (score desc, item asc).
-template <int KM>
-__device__ __forceinline__ void topk_insert(float (&tv)[KM], int (&ti)[KM], float s, int it) {
-#pragma unroll
-  for (int j = 0; j < KM; ++j) {
-    const bool sw = s > tv[j] || (s == tv[j] && it < ti[j]);
-    const float t = tv[j];
-    const int q = ti[j];
-    tv[j] = sw ? s : t;
-    ti[j] = sw ? it : q;
-    s = sw ? t : s;
-    it = sw ? q : it;
-  }
-}
 
 // Items per LDS tile and per-lane candidate buffer depth, per embedding dim
 // (LDS: 2 tiles of TILE x (D+4) floats + CB x 512 float2 <= 160 KB).
@@ -631,19 +604,6 @@ __global__ __launch_bounds__(256) void eval_sum_kernel(EvalTermParams P, double 
 // ---------------------------------------------------------------------------
 static int full_km(int k_max) { return k_max <= 16 ? 16 : (k_max <= 24 ? 24 : 32); }
 
-// Item splits so that small user counts still fill the chip (>= 4 workgroups
-// per CU), each split at least 4 tiles, at most 32 (merge: 2 lists per split
-// on one wave).
-static long full_splits(long n_users, int n_items, int cus) {
-  const long blocks = (n_users + FULL_USERS - 1) / FULL_USERS;
-  const long want = 4l * cus;
-  long s = blocks >= want ? 1 : (want + blocks - 1) / blocks;
-  const long max_s = (n_items + FULL_TILE * 4 - 1) / (FULL_TILE * 4);
-  s = s > max_s ? max_s : s;
-  s = s > 32 ? 32 : s;
-  return s < 1 ? 1 : s;
-}
-
 struct EvalLayout {
   size_t covered, partial, lscore, litem, total;
   long n_chunks, batch, splits;
@@ -661,7 +621,7 @@ static EvalLayout eval_layout(const bbgr_eval_args *a, bool full, int cus) {
                            EVAL_NTERM);
   if (full) {
     L.batch = a->n_users < FULL_BATCH ? a->n_users : FULL_BATCH;
-    L.splits = full_splits(L.batch, a->n_items, cus);
+    L.splits = full_splits(L.batch, a->n_items, cus, FULL_USERS);
     L.km = full_km(a->k_max);
     const size_t n = (size_t)(L.batch > 0 ? L.batch : 1) * L.splits * 2 * L.km;
     L.lscore = off;
@@ -671,16 +631,6 @@ static EvalLayout eval_layout(const bbgr_eval_args *a, bool full, int cus) {
   }
   L.total = off;
   return L;
-}
-
-static int device_cus() {
-  int dev = 0, cus = 256;
-  if (hipGetDevice(&dev) == hipSuccess) {
-    hipDeviceProp_t p;
-    if (hipGetDeviceProperties(&p, dev) == hipSuccess && p.multiProcessorCount > 0)
-      cus = p.multiProcessorCount;
-  }
-  return cus;
 }
 
 static int check_common(const bbgr_eval_args *a, const char *who) {
@@ -1047,4 +997,31 @@ extern "C" int bbgr_eval_full(const bbgr_eval_args *a, void *workspace, size_t *
     if (rc) return rc;
   }
   return launch_terms(a, true, L, ws, st);
+}
+
+extern "C" int bbgr_eval_lists(const bbgr_eval_args *a, void *workspace, size_t *workspace_bytes,
+                               bbgr_stream_t stream) {
+  BBGR_REQUIRE(a, "bbgr_eval_lists: null args");
+  BBGR_REQUIRE(a->n_users >= 0 && a->n_items > 0 && a->k_max > 0 && a->n_k > 0 && a->n_k <= 8,
+               "bbgr_eval_lists: sizes out of range (n_items > 0, k_max > 0, 1 <= n_k <= 8)");
+  BBGR_REQUIRE(a->k_max <= EVAL_LISTS_MAX_K, "bbgr_eval_lists: k_max <= 128");
+  for (int q = 0; q < a->n_k; ++q)
+    if (!(a->ks[q] > 0 && a->ks[q] <= a->k_max)) {
+      set_error("bbgr_eval_lists: ks[%d] = %d not in [1, k_max]", q, a->ks[q]);
+      return BBGR_ERR_INVALID;
+    }
+  BBGR_REQUIRE(a->n_users == 0 || (a->users && a->te_indptr && a->te_indices && a->topk &&
+                                   a->item_pop && a->sums),
+               "bbgr_eval_lists: null array (users, te_indptr, te_indices, topk, item_pop, sums)");
+  BBGR_REQUIRE(workspace_bytes, "bbgr_eval_lists: null workspace_bytes");
+  const EvalLayout L = eval_layout(a, false, 0);
+  if (!workspace) {
+    *workspace_bytes = L.total;
+    return BBGR_OK;
+  }
+  if (*workspace_bytes < L.total) {
+    set_error("bbgr_eval_lists: workspace %zu < %zu bytes", *workspace_bytes, L.total);
+    return BBGR_ERR_WORKSPACE;
+  }
+  return launch_terms(a, true, L, static_cast<char *>(workspace), as_stream(stream));
 }

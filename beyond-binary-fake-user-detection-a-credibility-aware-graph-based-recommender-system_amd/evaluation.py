@@ -285,7 +285,9 @@ def evaluate_full(user_emb: torch.Tensor, item_emb: torch.Tensor, train_csr: Csr
 # the first five only and return precision / recall / ndcg per K. The
 # wrappers below keep those signatures (the cfg fields as keyword arguments
 # with the reference's defaults) and return the same dictionaries. Sampled
-# candidates are drawn on the device (Philox), not from the host Generator.
+# candidates come from the reference's own numpy stream, drawn on the host
+# (candidates="numpy", the default), or from the device's Philox stream
+# (candidates="philox").
 _V1_KEYS = ("precision", "recall", "ndcg", "users_eval", "mode")
 
 

@@ -108,6 +108,9 @@ __all__ = ["build_cred_weighted_mats", "CredLightGCN", "evaluate_sampled"]
 
 def evaluate_sampled(model, train_csr, test_csr, num_items: int, device: str, **cfg):
     """lightgcn_cu.py:487-547 (same arguments; precision / recall / ndcg per K):
-    bbgr.evaluation.evaluate_sampled, candidates drawn on the device."""
+    bbgr.evaluation.evaluate_sampled_reference: the candidates are the reference's own
+    numpy stream (np.random.default_rng(seed + 999), drawn on the host by
+    bbgr_eval_draw_candidates), scored on the device in one launch;
+    candidates="philox" draws them on the device instead."""
     from .evaluation import evaluate_sampled_reference
     return evaluate_sampled_reference(model, train_csr, test_csr, num_items, device, **cfg)

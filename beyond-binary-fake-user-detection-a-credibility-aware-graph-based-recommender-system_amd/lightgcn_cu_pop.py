@@ -106,8 +106,10 @@ def evaluate_sampled(model, train_csr, test_csr, num_items: int, device: str, it
                      total_train_interactions: int, cred_np, **cfg):
     """Version-2/lighgcn_cu_pop.py:536-650 (same arguments, the same result
     dictionary per K; cfg.Ks / sampled_negatives / cred_group_pct / seed as
-    keyword arguments): one device launch for all users
-    (bbgr.evaluation.evaluate_sampled; candidates drawn by Philox)."""
+    keyword arguments): bbgr.evaluation.evaluate_sampled_reference: the candidates are the reference's own
+    numpy stream (np.random.default_rng(seed + 999), drawn on the host by
+    bbgr_eval_draw_candidates), scored on the device in one launch;
+    candidates="philox" draws them on the device instead."""
     from .evaluation import evaluate_sampled_reference
     return evaluate_sampled_reference(model, train_csr, test_csr, num_items, device, item_pop,
                                       total_train_interactions, cred_np, **cfg)

@@ -20,7 +20,10 @@ def build_message_passing_mats(train_edges_2xE, num_users: int, num_items: int, 
 
 def evaluate_sampled(model, train_csr, test_csr, num_items: int, device: str, **cfg):
     """version_1/lightgcn_cu_pop_long_tail_exposure.py:485-545 (same arguments; precision / recall / ndcg per K):
-    bbgr.evaluation.evaluate_sampled, candidates drawn on the device."""
+    bbgr.evaluation.evaluate_sampled_reference: the candidates are the reference's own
+    numpy stream (np.random.default_rng(seed + 999), drawn on the host by
+    bbgr_eval_draw_candidates), scored on the device in one launch;
+    candidates="philox" draws them on the device instead."""
     from .evaluation import evaluate_sampled_reference
     return evaluate_sampled_reference(model, train_csr, test_csr, num_items, device, **cfg)
 

@@ -23,7 +23,7 @@ import torch
 from . import _lib
 from ._lib import OP_GS, OP_J, OP_METHOD_A, OP_SYM, call, ld, ptr, stream_handle
 from .bpr import bpr_args
-from .graph import BipartiteGraph
+from .graph import BipartiteGraph, Csr
 from .optim import AdamRows, DeviceStepState, adam_step
 from .propagate import ORDER_GS, ORDER_J, ListLength, OperatorPair, backward, forward
 from .sampler import PopMixSampler, nonempty_rows, shuffle
@@ -505,6 +505,35 @@ class FusedTrainer:
         uf, itf = forward(self.pair, self.user_w, self.item_w, self.K, self.order,
                           out_u=self.uf, out_i=self.itf, ws=self.ws)
         return _input_rows(self.graph.user_order, uf), _input_rows(self.graph.item_order, itf)
+
+    def _train_rows(self) -> Csr:
+        """The graph's user -> item rows by INPUT id (rows and columns), columns
+        ascending: the graph's own CSR in input order, else built once."""
+        g = self.graph
+        if g.user_order is None and g.item_order is None and g.user_csr.cols_sorted:
+            return g.user_csr
+        if getattr(self, "_train_rows_csr", None) is None:
+            uc = g.user_csr
+            rows = torch.repeat_interleave(torch.arange(self.U, device=uc.indptr.device),
+                                           uc.degrees().long())
+            cols = uc.indices[:uc.nnz].long()
+            if g.user_order is not None:
+                rows = g.user_order.to_input(rows)
+            if g.item_order is not None:
+                cols = g.item_order.to_input(cols)
+            self._train_rows_csr = Csr(rows.int(), cols.int(), self.U, self.I, uc.indptr.device)
+        return self._train_rows_csr
+
+    def recommend(self, users, k: int, exclude_train: bool = True, item_mask=None,
+                  return_scores: bool = False):
+        """The top-k items of `users` (input ids) under the current weights:
+        forward(), then recommend.recommend on the final tables, the users'
+        train items left out unless exclude_train=False. int32 [n, k] item
+        input ids (and float32 scores), -1 (-inf) past the eligible items."""
+        from .recommend import recommend
+        uf, itf = self.forward()
+        return recommend(uf, itf, users, k, exclude=self._train_rows() if exclude_train else None,
+                         item_mask=item_mask, return_scores=return_scores)
 
     def batch(self):
         """(users, pos, neg) of the last step, as input ids (int64)."""

@@ -927,6 +927,55 @@ int bbgr_eval_draw_candidates(bbgr_pcg64 *rng, int64_t n_users, const int64_t *u
                               const int64_t *tr_indptr, const int64_t *tr_indices,
                               int64_t n_items, int32_t n_neg, int32_t *cand);
 
+/* The metrics reduction of the full protocol over CALLER-SUPPLIED lists       */
+/* (added under ABI 12): sums[n_k*11] exactly as bbgr_eval_full forms them,   */
+/* from args->topk[n_users*k_max] (entries of -1 are skipped: they hit        */
+/* nothing, cover nothing and do not count in the novelty means). The lists   */
+/* may come from bbgr_recommend. k_max <= 128; uf / itf / d, the train CSR    */
+/* and the sampled-only fields are ignored. Same two-call workspace idiom.    */
+int bbgr_eval_lists(const bbgr_eval_args *args, void *workspace, size_t *workspace_bytes,
+                    bbgr_stream_t stream);
+
+/* ------------------------------------------------------------------------- */
+/* Recommendation lists (added under ABI 12)                                  */
+/* The top-k items of users[n_users] (int64 rows of uf, any order, duplicates */
+/* allowed; every id in [0, n_user_rows)), 1 <= k <= 128, d in {64, 128,      */
+/* 256}. Scores are bbgr_eval_full's: <uf[u], itf[i]> as one fp32 fma chain   */
+/* over the components 0, d/2, 1, d/2+1, ... (fp32 MFMA); order is (score     */
+/* desc, item asc). Only finite scores rank.                                  */
+/* ex_indptr[n_user_rows+1] / ex_indices (nullable together): a CSR over user */
+/*   ids of items to leave out, rows sorted ascending, duplicates allowed.    */
+/*   Excluded items are dropped, not scored low.                              */
+/* item_mask (nullable, uint8 [n_items]): nonzero = eligible.                 */
+/* topk[n_users*k] int32, topk_score[n_users*k] float (nullable): a user with */
+/*   fewer than k eligible items gets -1 / -INFINITY in the tail.             */
+/* k above the kernel's register list depth (16 or 24) runs ceil(k / depth)   */
+/* scoring passes, each continuing after the last pair of the one before;     */
+/* the result is the exact top-k. workspace == NULL queries the size;         */
+/* n_users == 0 returns BBGR_OK without a launch. BBGR_ERR_INVALID names the  */
+/* offending field; d outside {64, 128, 256} is BBGR_ERR_UNSUPPORTED.         */
+/* ------------------------------------------------------------------------- */
+typedef struct {
+  int64_t n_users;
+  const int64_t *users;
+  int64_t n_user_rows;
+  const float *uf;
+  int64_t lduf;
+  const float *itf;
+  int64_t ldif;
+  int32_t d;
+  int32_t n_items;
+  int32_t k;
+  const int32_t *ex_indptr;
+  const int32_t *ex_indices;
+  const uint8_t *item_mask;
+  int32_t *topk;
+  float *topk_score;
+} bbgr_recommend_args;
+
+int bbgr_recommend(const bbgr_recommend_args *args, void *workspace, size_t *workspace_bytes,
+                   bbgr_stream_t stream);
+
 /* ------------------------------------------------------------------------- */
 /* Blueprint names (SURVEY §8(b)'s ABI sketch), thin forms of the above.      */
 /* ------------------------------------------------------------------------- */

@@ -23,6 +23,15 @@ roofline = eval_sampled_kernel: algorithmic bytes per user = (1 + n_neg + 1)
 cpu_baseline = the reference's per-user loop restated in oracle/ref_numpy.py
         (evaluate_sampled_reference_style, numpy RNG + searchsorted rejection +
         per-user scoring and metrics) on a bounded sample of users.
+--recommend: recommendation lists (bbgr_recommend) beside the full-ranking
+        scorer, raw C-ABI calls alternating in one process, HIP events around
+        each: `eval_full` (scorer + merge + metrics), `eval_lists` (the same
+        metrics kernels alone; eval_full - eval_lists = its scorer + merge),
+        `recommend` at k = --k (one pass) and at k = --k-long (continuation
+        passes). With --max-users N the graph is drawn over N users with the
+        config's degree law and item set (the tables keep the config's item
+        count and --dim or the config's width); the listed users are those
+        with test items. d = 256 has no eval_full arm (unsupported there).
 Prints ONE JSON line on stdout.
 """
 from __future__ import annotations
@@ -33,6 +42,8 @@ import os
 import sys
 import time
 
+import ctypes
+
 import numpy as np
 import torch
 
@@ -42,7 +53,8 @@ sys.path.insert(0, ROOT)
 import bbgr  # noqa: E402,F401
 from bbgr.evaluation import evaluate_full, evaluate_sampled  # noqa: E402
 from bbgr.graph import Csr  # noqa: E402
-from bbgr.synthetic import CONFIGS, config_edges, synthetic_credibility  # noqa: E402
+from bbgr.synthetic import (CONFIGS, CONFIG_SEED, config_edges, synthetic_credibility,  # noqa: E402
+                            synthetic_edges)
 
 HBM_PEAK_GBS = 8000.0
 FP32_MFMA_PEAK_TF = 157.3   # MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32 dense peak
@@ -56,6 +68,118 @@ def split(edges, frac, seed):
     rng = np.random.default_rng([seed, 0x7E57])
     test = rng.random(edges.shape[1]) < frac
     return np.ascontiguousarray(edges[:, ~test]), np.ascontiguousarray(edges[:, test])
+
+
+def bench_recommend(args):
+    """The --recommend arms (see the module docstring)."""
+    from bbgr import _lib
+    from bbgr import evaluation as EV
+    from bbgr.recommend import recommend
+    cfg = CONFIGS[args.config]
+    U, I, d = cfg["num_users"], cfg["num_items"], args.dim or cfg["emb_dim"]
+    dev = "cuda"
+    if args.max_users and args.max_users < U:
+        E = int(cfg["num_edges"] * (args.max_users / U))
+        U = args.max_users
+        edges = synthetic_edges(U, I, E, CONFIG_SEED[args.config], items=cfg["items"])
+    else:
+        edges = config_edges(args.config)
+    tr, te = split(edges, 0.2, 5)
+    del edges
+    trc, tec = Csr(tr[0], tr[1], U, I, dev), Csr(te[0], te[1], U, I, dev)
+    g = torch.Generator(device=dev).manual_seed(7)
+    uf = (torch.rand(U, d, device=dev, generator=g) - 0.5)
+    itf = (torch.rand(I, d, device=dev, generator=g) - 0.5)
+    pop_t = torch.tensor(np.bincount(tr[1], minlength=I).astype(np.float32), device=dev)
+    users = EV._eval_users(tec)
+    n = users.numel()
+    log(f"[recommend] {args.config}: {n} listed users x {I} items, d {d}")
+    k, kl = args.k, args.k_long
+    with_full = d in (64, 128) and k <= 32
+    i32 = dict(dtype=torch.int32, device=dev)
+    groups = torch.zeros(n, dtype=torch.uint8, device=dev)
+    sums = torch.empty(EV.NOUT, dtype=torch.float64, device=dev)
+    topk_full = torch.empty(n * k, **i32)
+    ea = EV._args(users, trc, tec, uf, itf, I, (k,), pop_t, int(tr.shape[1]), groups, sums)
+    ea.topk = topk_full.data_ptr()
+
+    def rec_args(kk):
+        out = torch.empty(n * kk, **i32)
+        a = _lib.RecommendArgs()
+        a.n_users, a.users, a.n_user_rows = n, users.data_ptr(), U
+        a.uf, a.lduf, a.itf, a.ldif = uf.data_ptr(), d, itf.data_ptr(), d
+        a.d, a.n_items, a.k = d, I, kk
+        a.ex_indptr, a.ex_indices = trc.indptr.data_ptr(), trc.indices.data_ptr()
+        a.topk = out.data_ptr()
+        return a, out
+
+    arms = {}
+    if with_full:
+        arms["eval_full"] = ("bbgr_eval_full", ea)
+        arms["eval_lists"] = ("bbgr_eval_lists", ea)
+    ra, topk_rec = rec_args(k)
+    arms["recommend"] = ("bbgr_recommend", ra)
+    rl, _long = rec_args(kl)
+    arms["recommend_long"] = ("bbgr_recommend", rl)
+    ws = {}
+    for name, (fn, a) in arms.items():
+        ws[name] = EV._run(fn, a, dev)   # sizes the workspace; first (warm-up) call
+    st = _lib.stream_handle()
+    s = torch.cuda.current_stream()
+
+    def once(name):
+        fn, a = arms[name]
+        nb = ctypes.c_size_t(ws[name].numel())
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(s)
+        _lib.call(fn, ctypes.byref(a), ws[name].data_ptr(), ctypes.byref(nb), st)
+        e1.record(s)
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1)
+
+    for _ in range(args.warmup):
+        for name in arms:
+            once(name)
+    ms = {name: [] for name in arms}
+    for _ in range(args.reps):   # the arms alternate inside every round
+        for name in arms:
+            ms[name].append(once(name))
+    stat = {name: {"median_ms": float(np.median(v)), "min_ms": float(np.min(v)),
+                   "max_ms": float(np.max(v))} for name, v in ms.items()}
+    flops = 2.0 * n * I * d
+    tf = lambda t_ms: flops / (t_ms * 1e-3) / 1e12   # noqa: E731
+    km = 16 if (k + 15) // 16 <= (k + 23) // 24 else 24
+    kml = 16 if (kl + 15) // 16 <= (kl + 23) // 24 else 24
+    passes, passes_long = -(-k // km), -(-kl // kml)
+    rec = stat["recommend"]["median_ms"]
+    line = {
+        "metric": "recommend_users_per_s", "value": n / (rec * 1e-3), "unit": "users/s",
+        "n_gpus": 1, "steps": args.reps, "warmup": args.warmup + 1, "ms_per_step": rec,
+        "higher_is_better": True, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": f"{args.config} recommend (all items, train rows excluded)",
+                   "users": n, "num_items": I, "emb_dim": d, "k": k, "k_long": kl,
+                   "train_edges": int(tr.shape[1])},
+        "arms_ms": stat,
+        "recommend": {"k": k, "passes": passes, "list_depth": km, "tflops": tf(rec),
+                      "frac_fp32_mfma_peak": tf(rec) / FP32_MFMA_PEAK_TF},
+        "recommend_long": {"k": kl, "passes": passes_long, "list_depth": kml,
+                           "ms": stat["recommend_long"]["median_ms"],
+                           "x_single_pass": stat["recommend_long"]["median_ms"] / rec},
+        "note": "HIP events around each raw C-ABI call; frac = 2*users*items*d flops of ONE "
+                "scoring pass over the call's time, against the fp32 MFMA dense peak",
+    }
+    if with_full:
+        sm = stat["eval_full"]["median_ms"] - stat["eval_lists"]["median_ms"]
+        line["eval_full_scorer_merge_ms"] = sm
+        line["eval_full_scorer_merge_frac_peak"] = tf(sm) / FP32_MFMA_PEAK_TF
+        line["recommend_over_eval_full_scorer_merge"] = rec / sm
+        # same lists wherever no train item reaches eval_full's top-k (always, at these sizes)
+        line["lists_equal_eval_full"] = bool(torch.equal(topk_full, topk_rec))
+    chk = recommend(uf, itf, users[:4096], kl, exclude=trc)
+    line["long_prefix_equals_short"] = bool(torch.equal(chk[:, :k],
+                                                        topk_rec.view(n, k)[:4096]))
+    log(json.dumps(line, indent=1))
+    print(json.dumps(line), flush=True)
 
 
 def main():
@@ -74,7 +198,15 @@ def main():
                     help="sampled: device Philox candidates, or the reference's numpy stream")
     ap.add_argument("--max-users", type=int, default=0,
                     help="evaluate only the first N users with test items (0 = all)")
+    ap.add_argument("--recommend", action="store_true",
+                    help="recommendation lists beside the full-ranking scorer (see above)")
+    ap.add_argument("--dim", type=int, default=0, help="--recommend: table width (0 = config's)")
+    ap.add_argument("--k", type=int, default=10, help="--recommend: the single-pass list length")
+    ap.add_argument("--k-long", type=int, default=100,
+                    help="--recommend: a list length that needs continuation passes")
     args = ap.parse_args()
+    if args.recommend:
+        return bench_recommend(args)
     cfg = CONFIGS[args.config]
     U, I, d = cfg["num_users"], cfg["num_items"], cfg["emb_dim"]
     dev = "cuda"
