@@ -145,6 +145,35 @@ class RecommendArgs(ctypes.Structure):
     ]
 
 
+SLAS_VIEW = {None: 0, "early": 1, "late": 2}   # bbgr_slas_view
+
+
+class SlasSampleArgs(ctypes.Structure):
+    """bbgr_slas_sample_args (bbgr_slas_sample)."""
+    _fields_ = [
+        ("n", c_int64), ("rows", c_void_p), ("n_rows", c_int64),
+        ("indptr", c_void_p), ("nbr", c_void_p), ("eid", c_void_p),
+        ("row_profile", c_void_p), ("nbr_profile", c_void_p),
+        ("F", c_int32), ("kappa", c_float), ("k", c_int32),
+        ("ts", c_void_p), ("ts_stride", c_int64), ("view", c_int32), ("split", c_float),
+        ("label", c_void_p), ("upweight", c_float),
+        ("seed", c_uint64), ("counter", ctypes.c_uint32), ("stage", ctypes.c_uint32),
+        ("out_nbr", c_void_p), ("out_eid", c_void_p), ("out_count", c_void_p),
+    ]
+
+
+class SlasInduceArgs(ctypes.Structure):
+    """bbgr_slas_induce_args (bbgr_slas_induce)."""
+    _fields_ = [
+        ("n_users_listed", c_int64), ("users", c_void_p), ("n_users", c_int64),
+        ("item_local", c_void_p),
+        ("indptr", c_void_p), ("nbr", c_void_p), ("eid", c_void_p),
+        ("ts", c_void_p), ("ts_stride", c_int64), ("view", c_int32), ("split", c_float),
+        ("count", c_void_p), ("out_edges", c_void_p), ("out_eid", c_void_p),
+        ("capacity", c_int64),
+    ]
+
+
 class Pcg64State(ctypes.Structure):
     """bbgr_pcg64: numpy's PCG64 bit_generator.state (128-bit state and
     increment as two 64-bit halves, the buffered 32-bit output)."""
@@ -280,6 +309,12 @@ _SIGNATURES = {
                              _P], c_int32),
     "bbgr_rows_add_unique": ([c_int64, _P, _P, c_int64, _P, c_int64, c_int32, c_int64, _P],
                              c_int32),
+    "bbgr_slas_profiles": ([c_int32, c_int32, c_int32, _P, c_int64, _P, _P, _P, _P, _P],
+                           c_int32),
+    "bbgr_slas_sample": ([ctypes.POINTER(SlasSampleArgs), _P], c_int32),
+    "bbgr_mark_ids32": ([c_int64, _P, ctypes.c_uint8, _P, c_int64, _P], c_int32),
+    "bbgr_slas_induce": ([ctypes.POINTER(SlasInduceArgs), _P, ctypes.POINTER(c_size_t), _P],
+                         c_int32),
     # blueprint names, thin forms of the entry points above
     "bbgr_spmm_f32": ([ctypes.POINTER(CsrStruct), _P, c_int64, _P, c_int64, c_int32, _P, _P,
                        _P, c_float, _P], c_int32),

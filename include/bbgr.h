@@ -977,6 +977,125 @@ int bbgr_recommend(const bbgr_recommend_args *args, void *workspace, size_t *wor
                    bbgr_stream_t stream);
 
 /* ------------------------------------------------------------------------- */
+/* SLAS subgraph sampling for the credibility GNN (added under ABI 12)        */
+/*   Replaces build_slas_subgraph and its helpers, main.py:727-883: a host    */
+/*   loop per seed user, per sampled item and per edge of every subgraph      */
+/*   user, three times per training step.                                     */
+/* The reference-order CSR (build_csr_from_src, main.py:739-749, a stable     */
+/* sort by source): indptr[n_rows+1], and per slot the neighbour id nbr[] and */
+/* the input edge id eid[], a row's slots in ascending edge id. One way to    */
+/* build it: bbgr_csr_build with the edge id as the column (n_cols = E); its  */
+/* indices are then eid[], and nbr[] = dst[eid[]].                            */
+/* view: BBGR_SLAS_VIEW_EARLY keeps the slots with ts[eid * ts_stride] <      */
+/* split, BBGR_SLAS_VIEW_LATE those with ts >= split (a value equal to split  */
+/* is late); ts is one float per edge id (pointer + stride in floats, so a    */
+/* column of edge_attr is passed in place) and may be NULL with VIEW_NONE.    */
+/* ------------------------------------------------------------------------- */
+typedef enum {
+  BBGR_SLAS_VIEW_NONE = 0,
+  BBGR_SLAS_VIEW_EARLY = 1,
+  BBGR_SLAS_VIEW_LATE = 2
+} bbgr_slas_view;
+
+/* Similarity profiles (main.py:727-737), fp32 row-major, 1 <= F <= 16:       */
+/*   item_norm[i] = item_x[i] / (|item_x[i]|_2 + 1e-12)      [n_items, F]     */
+/*   user_mu[u]   = l2n((sum over the slots of row u of item_norm[nbr_u]) /   */
+/*                  max(deg_u, 1)), with multiplicity        [n_users, F]     */
+/* l2n in the same + 1e-12 form. item_x has leading dimension ldx >= F. The   */
+/* sums run in a fixed order without float atomics: two calls, same bits.     */
+int bbgr_slas_profiles(int32_t n_users, int32_t n_items, int32_t F, const float *item_x,
+                       int64_t ldx, const int32_t *indptr_u, const int32_t *nbr_u,
+                       float *item_norm, float *user_mu, bbgr_stream_t stream);
+
+/* A weighted sample without replacement of at most k slots of each listed    */
+/* row (slas_sample_items_for_user / slas_sample_users_for_item,              */
+/* main.py:758-807; one entry point serves both directions). With m eligible  */
+/* slots (after the view filter): m == 0 gives count 0; m <= k gives every    */
+/* eligible slot in row order (no randomness); otherwise slot j has the       */
+/* weight w_j = exp(kappa * <nbr_profile[nbr_j], row_profile[row]>) in fp32,  */
+/* times (1 + upweight) where label[nbr_j] >= 0 (label nullable, int64 per    */
+/* neighbour-side id), and the key -log(U_j) / w_j; the k smallest keys win,  */
+/* written in ascending key order, equal keys the lower slot first. These     */
+/* exponential clocks are successive sampling with probabilities proportional */
+/* to w: the distribution of rng.choice(m, k, replace=False, p=w/sum(w)).     */
+/* U_j in (0, 1] is the first word of Philox4x32-10 with key = seed and       */
+/* counter = {counter, stage, row id, slot position in the row}: a row's      */
+/* picks are a pure function of seed, counter, stage and that row, whatever   */
+/* else is listed and however the launch is shaped. stage in [0, 255].        */
+/* rows[n]: int64 global row ids (outside [0, n_rows): count 0).              */
+/* out_nbr / out_eid [n, k] int32, unused entries -1; out_count[n] int32.     */
+/* Duplicate edges are separate slots: out_eid never repeats within a row.    */
+/* One wave per row, the running best k held one per lane and merged with     */
+/* each 64-slot chunk across the lanes; a row above 1024 slots is dealt out   */
+/* to the 16 waves of a workgroup (same picks): no row is bound by one lane's */
+/* loop, and a hub row not by one wave's.                                     */
+/* 1 <= k <= 64, 1 <= F <= 16; n == 0 returns BBGR_OK without a launch.       */
+typedef struct {
+  int64_t n;
+  const int64_t *rows;
+  int64_t n_rows;
+  const int32_t *indptr;
+  const int32_t *nbr;
+  const int32_t *eid;
+  const float *row_profile;  /* [n_rows, F] */
+  const float *nbr_profile;  /* [neighbour-side rows, F] */
+  int32_t F;
+  float kappa;
+  int32_t k;
+  const float *ts;           /* nullable with BBGR_SLAS_VIEW_NONE */
+  int64_t ts_stride;
+  int32_t view;
+  float split;
+  const int64_t *label;      /* nullable */
+  float upweight;
+  uint64_t seed;
+  uint32_t counter;
+  uint32_t stage;
+  int32_t *out_nbr;
+  int32_t *out_eid;
+  int32_t *out_count;
+} bbgr_slas_sample_args;
+int bbgr_slas_sample(const bbgr_slas_sample_args *args, bbgr_stream_t stream);
+
+/* mask[ids[j]] = value for j < n where 0 <= ids[j] < n_rows: the marking of  */
+/* a -1-padded int32 list (bbgr_slas_sample's out_nbr); with                   */
+/* bbgr_mask_to_list the ascending distinct ids (np.unique, main.py:815,820). */
+int bbgr_mark_ids32(int64_t n, const int32_t *ids, uint8_t value, uint8_t *mask,
+                    int64_t n_rows, bbgr_stream_t stream);
+
+/* The induced edge list (main.py:835-856): for each user of users[] in list  */
+/* order (distinct global ids), over its row of the user-row CSR in row       */
+/* order, every eligible slot (view filter) whose item is sampled             */
+/* (item_local[nbr] >= 0; int32 [n_items], -1 = not sampled) emits (position  */
+/* of the user in users[], item_local[nbr], eid): the reference's order.      */
+/* Two calls over ONE workspace (size query with workspace == NULL):          */
+/*   out_edges == NULL: count and exclusive scan; *count (DEVICE int64) =     */
+/*     the number of edges, per-user offsets stay in the workspace;           */
+/*   out_edges != NULL: fill out_edges[2, capacity] int64 (row 0 local user,  */
+/*     row 1 local item) and out_eid[capacity] int64 from those offsets;      */
+/*     capacity = the count the caller read (entries past it are dropped).    */
+/* n_users_listed == 0 returns BBGR_OK without a launch (*count untouched).   */
+typedef struct {
+  int64_t n_users_listed;
+  const int64_t *users;
+  int64_t n_users;            /* rows of the CSR (bounds check) */
+  const int32_t *item_local;
+  const int32_t *indptr;
+  const int32_t *nbr;
+  const int32_t *eid;
+  const float *ts;
+  int64_t ts_stride;
+  int32_t view;
+  float split;
+  int64_t *count;
+  int64_t *out_edges;
+  int64_t *out_eid;
+  int64_t capacity;
+} bbgr_slas_induce_args;
+int bbgr_slas_induce(const bbgr_slas_induce_args *args, void *workspace,
+                     size_t *workspace_bytes, bbgr_stream_t stream);
+
+/* ------------------------------------------------------------------------- */
 /* Blueprint names (SURVEY §8(b)'s ABI sketch), thin forms of the above.      */
 /* ------------------------------------------------------------------------- */
 /* Y = diag(row_scale) A diag(col_scale) X (either scale NULL = ones), one    */
