@@ -97,6 +97,11 @@ class SpmmArgs(ctypes.Structure):
     ]
 
 
+class SpmmBf16Io(ctypes.Structure):
+    """bbgr_spmm_bf16_io (bbgr_spmm_bf16): the bf16 x / y tables."""
+    _fields_ = [("x", c_void_p), ("ldx", c_int64), ("y", c_void_p), ("ldy", c_int64)]
+
+
 class BprArgs(ctypes.Structure):
     _fields_ = [
         ("batch", c_int64), ("d", c_int32),
@@ -238,6 +243,9 @@ _SIGNATURES = {
     "bbgr_relabel": ([c_int64, _P, _P, _P, _P], c_int32),
     "bbgr_spmm": ([ctypes.POINTER(CsrStruct), ctypes.POINTER(SpmmArgs), _P], c_int32),
     "bbgr_epilogue": ([c_int32, _P, c_int64, ctypes.POINTER(SpmmArgs), _P], c_int32),
+    "bbgr_to_bf16": ([c_int64, c_int32, _P, c_int64, _P, c_int64, _P], c_int32),
+    "bbgr_spmm_bf16": ([ctypes.POINTER(CsrStruct), ctypes.POINTER(SpmmArgs),
+                        ctypes.POINTER(SpmmBf16Io), _P], c_int32),
     "bbgr_bpr": ([ctypes.POINTER(BprArgs), _P], c_int32),
     "bbgr_bpr_reduce": ([c_int64, _P, c_float, c_float, _P, _P], c_int32),
     "bbgr_adam": ([c_int64, _P, _P, _P, _P, c_float, c_double, c_double, c_float,

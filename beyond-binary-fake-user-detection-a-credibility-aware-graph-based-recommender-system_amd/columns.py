@@ -75,6 +75,8 @@ class ColumnShardedTrainer(FusedTrainer):
                  device=None, group=None, u0=None, i0=None, seed: int = 42,
                  vertex_order: str = "degree", column_parts: int | None = None,
                  column_index: int | None = None, **kw):
+        if "forward_dtype" in kw:   # column slices may be narrower than the bf16 kernels' 64
+            raise ValueError("ColumnShardedTrainer takes no forward_dtype (fp32 tables only)")
         self.group = group
         self.distributed = dist.is_available() and dist.is_initialized() and column_parts is None
         if self.distributed:

@@ -150,6 +150,56 @@ __device__ __forceinline__ float4 f4_mul(float a, float4 x) {
   return make_float4(a * x.x, a * x.y, a * x.z, a * x.w);
 }
 
+// Element type of the gathered table x and of the y table (compile-time BF of
+// the gathers and the epilogue): fp32, or bf16 (bbgr_spmm_bf16; SpmmParams
+// then carries the 2-byte tables' addresses in x / y, ldx / ldy in elements).
+// A lane keeps its columns (4*lane .. 4*lane+3, +64k): 8 bytes per load
+// instead of 16, widened by a 16-bit shift (exact) when they are added, so
+// every sum is the fp32 kernel's on the widened table, operation for operation.
+template <bool BF> struct RowVec { using type = float4; };
+template <> struct RowVec<true> { using type = uint2; };
+typedef unsigned u2v __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ uint2 ld_nt(const uint2 *p) {
+  const u2v v = __builtin_nontemporal_load(reinterpret_cast<const u2v *>(p));
+  return make_uint2(v.x, v.y);
+}
+__device__ __forceinline__ void st_nt(uint2 *p, uint2 v) {
+  u2v w;
+  w.x = v.x;
+  w.y = v.y;
+  __builtin_nontemporal_store(w, reinterpret_cast<u2v *>(p));
+}
+__device__ __forceinline__ float4 widen(float4 v) { return v; }
+__device__ __forceinline__ float4 widen(uint2 v) {
+  return make_float4(__uint_as_float(v.x << 16), __uint_as_float(v.x & 0xffff0000u),
+                     __uint_as_float(v.y << 16), __uint_as_float(v.y & 0xffff0000u));
+}
+template <bool BF>
+__device__ __forceinline__ typename RowVec<BF>::type zero_vec() {
+  if constexpr (BF) return make_uint2(0u, 0u);   // widens to +0.0
+  else return make_float4(0.f, 0.f, 0.f, 0.f);
+}
+// this lane's first column block of source row c
+template <bool BF>
+__device__ __forceinline__ const typename RowVec<BF>::type *src_row(const float *x, long ldx,
+                                                                    int c, int lane) {
+  if constexpr (BF)
+    return reinterpret_cast<const uint2 *>(reinterpret_cast<const uint16_t *>(x) + (long)c * ldx) +
+           lane;
+  else
+    return reinterpret_cast<const float4 *>(x + (long)c * ldx) + lane;
+}
+// fp32 -> bf16, round to nearest even (torch's conversion: a NaN becomes the
+// quiet NaN 0x7fc0; +-inf, +-0 and subnormals follow from the integer form)
+__device__ __forceinline__ unsigned bf16_rne(float f) {
+  const unsigned u = __float_as_uint(f);
+  if ((u & 0x7fffffffu) > 0x7f800000u) return 0x7fc0u;
+  return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
+}
+__device__ __forceinline__ uint2 bf16_pack(float4 v) {
+  return make_uint2(bf16_rne(v.x) | (bf16_rne(v.y) << 16), bf16_rne(v.z) | (bf16_rne(v.w) << 16));
+}
+
 // Column indices and per-edge values are read once per launch (200 MB each at
 // C4). Streaming (non-temporal) loads for them, so they would not displace
 // gathered rows from L2 / the Infinity Cache, measured slower (round 4 A/B,
@@ -357,9 +407,10 @@ __device__ __forceinline__ int compact_live(int &my, float &mw) {
 constexpr bool kRowCompact = BBGR_ROW_COMPACT != 0;
 
 // Sum w_e * x[col_e] over edges [eb, ee) into acc (one 16-lane group).
-template <int D, int WMODE, bool MASKED, bool BITS = false, int TAG = TAG_NONE>
+template <int D, int WMODE, bool MASKED, bool BITS = false, int TAG = TAG_NONE, bool BF = false>
 __device__ __forceinline__ void gather_range(const SpmmParams &P, int eb, int ee,
                                              int lane, float4 (&acc)[D / 64]) {
+  using SV = typename RowVec<BF>::type;
   constexpr int V = D / 64;
   constexpr int U = Tune<D>::row_u;   // source rows in flight per group per batch
   for (int e0 = eb; e0 < ee; e0 += 16) {
@@ -408,7 +459,7 @@ __device__ __forceinline__ void gather_range(const SpmmParams &P, int eb, int ee
       }
     }
     for (int j0 = 0; j0 < n; j0 += U) {
-      float4 v[U][V];
+      SV v[U][V];
       int sl[U];   // the lanes of this round's edges
 #pragma unroll
       for (int j = 0; j < U; ++j) {
@@ -419,8 +470,7 @@ __device__ __forceinline__ void gather_range(const SpmmParams &P, int eb, int ee
         }
         const int c = __shfl(my, sl[j], 16);
         if (j0 + j < n && (!MASKED || c >= 0)) {
-          const float4 *src =
-              reinterpret_cast<const float4 *>(P.x + (long)c * P.ldx) + lane;
+          const SV *src = src_row<BF>(P.x, P.ldx, c, lane);
           if (c >= P.nt_from) {
 #pragma unroll
             for (int k = 0; k < V; ++k) v[j][k] = ld_nt(src + 16 * k);
@@ -430,18 +480,18 @@ __device__ __forceinline__ void gather_range(const SpmmParams &P, int eb, int ee
           }
         } else {
 #pragma unroll
-          for (int k = 0; k < V; ++k) v[j][k] = make_float4(0.f, 0.f, 0.f, 0.f);
+          for (int k = 0; k < V; ++k) v[j][k] = zero_vec<BF>();
         }
       }
 #pragma unroll
       for (int j = 0; j < U; ++j) {
         if (WMODE == 0) {
 #pragma unroll
-          for (int k = 0; k < V; ++k) acc[k] = f4_add(acc[k], v[j][k]);
+          for (int k = 0; k < V; ++k) acc[k] = f4_add(acc[k], widen(v[j][k]));
         } else {
           const float w = __shfl(mw, sl[j], 16);
 #pragma unroll
-          for (int k = 0; k < V; ++k) acc[k] = f4_fma(w, v[j][k], acc[k]);
+          for (int k = 0; k < V; ++k) acc[k] = f4_fma(w, widen(v[j][k]), acc[k]);
         }
       }
     }
@@ -561,13 +611,14 @@ __device__ __forceinline__ void gather_slot(const SpmmParams &P, int eb, int ee,
 }
 
 // A row's gather for any width: the narrow form below 64 columns.
-template <int D, int WMODE, bool MASKED, bool BITS = false, int TAG = TAG_NONE>
+template <int D, int WMODE, bool MASKED, bool BITS = false, int TAG = TAG_NONE, bool BF = false>
 __device__ __forceinline__ void gather_row(const SpmmParams &P, int eb, int ee, int lane,
                                            float4 (&acc)[RowShape<D>::V]) {
   if constexpr (D < 64) {
+    static_assert(!BF, "bf16 tables: d >= 64");
     gather_range_narrow<D, WMODE, MASKED>(P, eb, ee, lane, acc[0]);
   } else {
-    gather_range<D, WMODE, MASKED, BITS, TAG>(P, eb, ee, lane, acc);
+    gather_range<D, WMODE, MASKED, BITS, TAG, BF>(P, eb, ee, lane, acc);
   }
 }
 
@@ -582,10 +633,11 @@ __device__ __forceinline__ void gather_row(const SpmmParams &P, int eb, int ee, 
 #endif
 constexpr bool kPairCompact = BBGR_PAIR_COMPACT != 0;
 
-template <int D, int WMODE, bool MASKED, int TAG = TAG_NONE>
+template <int D, int WMODE, bool MASKED, int TAG = TAG_NONE, bool BF = false>
 __device__ __forceinline__ void gather_pair(const SpmmParams &P, int ebA, int eeA, int ebB,
                                             int eeB, int lane, float4 (&accA)[D / 64],
                                             float4 (&accB)[D / 64]) {
+  using SV = typename RowVec<BF>::type;
   constexpr int V = D / 64;
   constexpr int U = MASKED ? Tune<D>::pair_u_masked : Tune<D>::pair_u;   // per row
   const int nA = eeA - ebA, nB = eeB - ebB;
@@ -638,7 +690,7 @@ __device__ __forceinline__ void gather_pair(const SpmmParams &P, int ebA, int ee
     }
     const int nn = max(na, nb);
     for (int j0 = 0; j0 < nn; j0 += U) {
-      float4 vA[U][V], vB[U][V];
+      SV vA[U][V], vB[U][V];
       int sA[U], sB[U];   // the lanes of this round's edges
 #pragma unroll
       for (int j = 0; j < U; ++j) {
@@ -652,7 +704,7 @@ __device__ __forceinline__ void gather_pair(const SpmmParams &P, int ebA, int ee
         const int cA = __shfl(myA, sA[j], 16);
         const int cB = __shfl(myB, sB[j], 16);
         if (j0 + j < na && (!MASKED || cA >= 0)) {
-          const float4 *src = reinterpret_cast<const float4 *>(P.x + (long)cA * P.ldx) + lane;
+          const SV *src = src_row<BF>(P.x, P.ldx, cA, lane);
           if (cA >= P.nt_from) {
 #pragma unroll
             for (int k = 0; k < V; ++k) vA[j][k] = ld_nt(src + 16 * k);
@@ -662,10 +714,10 @@ __device__ __forceinline__ void gather_pair(const SpmmParams &P, int ebA, int ee
           }
         } else {
 #pragma unroll
-          for (int k = 0; k < V; ++k) vA[j][k] = make_float4(0.f, 0.f, 0.f, 0.f);
+          for (int k = 0; k < V; ++k) vA[j][k] = zero_vec<BF>();
         }
         if (j0 + j < nb && (!MASKED || cB >= 0)) {
-          const float4 *src = reinterpret_cast<const float4 *>(P.x + (long)cB * P.ldx) + lane;
+          const SV *src = src_row<BF>(P.x, P.ldx, cB, lane);
           if (cB >= P.nt_from) {
 #pragma unroll
             for (int k = 0; k < V; ++k) vB[j][k] = ld_nt(src + 16 * k);
@@ -675,7 +727,7 @@ __device__ __forceinline__ void gather_pair(const SpmmParams &P, int ebA, int ee
           }
         } else {
 #pragma unroll
-          for (int k = 0; k < V; ++k) vB[j][k] = make_float4(0.f, 0.f, 0.f, 0.f);
+          for (int k = 0; k < V; ++k) vB[j][k] = zero_vec<BF>();
         }
       }
 #pragma unroll
@@ -683,16 +735,16 @@ __device__ __forceinline__ void gather_pair(const SpmmParams &P, int ebA, int ee
         if (WMODE == 0) {
 #pragma unroll
           for (int k = 0; k < V; ++k) {
-            accA[k] = f4_add(accA[k], vA[j][k]);
-            accB[k] = f4_add(accB[k], vB[j][k]);
+            accA[k] = f4_add(accA[k], widen(vA[j][k]));
+            accB[k] = f4_add(accB[k], widen(vB[j][k]));
           }
         } else {
           const float wA = __shfl(mwA, sA[j], 16);
           const float wB = __shfl(mwB, sB[j], 16);
 #pragma unroll
           for (int k = 0; k < V; ++k) {
-            accA[k] = f4_fma(wA, vA[j][k], accA[k]);
-            accB[k] = f4_fma(wB, vB[j][k], accB[k]);
+            accA[k] = f4_fma(wA, widen(vA[j][k]), accA[k]);
+            accB[k] = f4_fma(wB, widen(vB[j][k]), accB[k]);
           }
         }
       }
@@ -752,12 +804,27 @@ __device__ __forceinline__ void adam_row(const SpmmParams &P, long row, long mro
   }
 }
 
-template <int D>
+template <int D, bool BF = false>
 __device__ __forceinline__ void epilogue(const SpmmParams &P, int row, int lane,
                                          const float4 (&T)[RowShape<D>::V]) {
   constexpr int V = RowShape<D>::V;
   if (lane >= RowShape<D>::LANES) return;   // narrow rows: idle lanes
-  if (P.y || P.adam_p) {
+  if constexpr (BF) {
+    // bf16 y table (no add, no fused Adam, no row map: refused by the entry):
+    // the fp32 value ys * T as below, rounded once to nearest even
+    if (P.y) {
+      const float ys = (P.y_scale ? P.y_scale[row] : 1.f) * P.y_scale_s;
+      uint2 *dst =
+          reinterpret_cast<uint2 *>(reinterpret_cast<uint16_t *>(P.y) + (long)row * P.ldy) + lane;
+      if (row >= P.nt_out_from) {
+#pragma unroll
+        for (int k = 0; k < V; ++k) st_nt(dst + 16 * k, bf16_pack(f4_mul(ys, T[k])));
+      } else {
+#pragma unroll
+        for (int k = 0; k < V; ++k) dst[16 * k] = bf16_pack(f4_mul(ys, T[k]));
+      }
+    }
+  } else if (P.y || P.adam_p) {
     const float ys = (P.y_scale ? P.y_scale[row] : 1.f) * P.y_scale_s;
     float4 G[V];
     const long ra = P.add_map ? (long)P.add_map[row] : (long)row;
@@ -847,7 +914,7 @@ __device__ __forceinline__ void block_reduce16(float4 *red, int g, int lane,
 // Fixed-order sum of a split row's chunk partials (slots base .. base+c-1):
 // group g adds slots g, g+16, ... in order, then the 16 group sums are added
 // in group order (block_reduce16); g == 0 runs the epilogue.
-template <int D>
+template <int D, bool BF = false>
 __device__ __forceinline__ void split_row_finish(const SpmmParams &P, int row, int base, int c,
                                                  float4 *red, int g, int lane) {
   constexpr int V = RowShape<D>::V;
@@ -867,7 +934,7 @@ __device__ __forceinline__ void split_row_finish(const SpmmParams &P, int row, i
     float4 T[V];
 #pragma unroll
     for (int k = 0; k < V; ++k) T[k] = red[lane + 16 * k];
-    epilogue<D>(P, row, lane, T);
+    epilogue<D, BF>(P, row, lane, T);
   }
 }
 
@@ -881,7 +948,7 @@ __device__ __forceinline__ void split_row_finish(const SpmmParams &P, int row, i
 // takes one agent-scope acquire before its workgroup reads the slots with
 // plain loads. The ticket lives at arrivals[base] (base = the row's first
 // chunk) and the reducer re-zeroes it.
-template <int D>
+template <int D, bool BF = false>
 __device__ __forceinline__ void split_row_arrive(const SpmmParams &P, int4 ch, float4 *red,
                                                  int g, int lane) {
   constexpr int V = RowShape<D>::V;
@@ -923,7 +990,7 @@ __device__ __forceinline__ void split_row_arrive(const SpmmParams &P, int4 ch, f
   __syncthreads();
   const int last = flag[0];
   __syncthreads();   // flag read before split_row_finish reuses red[]
-  if (last) split_row_finish<D>(P, ch.x, base, c, red, g, lane);
+  if (last) split_row_finish<D, BF>(P, ch.x, base, c, red, g, lane);
 }
 
 // A single-chunk long row (deg in (long_threshold, chunk_edges]) of a slot-
@@ -1038,7 +1105,7 @@ __device__ __forceinline__ bool serial_long(const SpmmParams &P, int len) {
 
 // Short-row workgroup sb of a launch: rows sb*per_block.. of the row range or
 // of the row list (whose length is n_list).
-template <int D, int WMODE, bool MASKED, bool PAIR, bool BITS, int TAG>
+template <int D, int WMODE, bool MASKED, bool PAIR, bool BITS, int TAG, bool BF = false>
 __device__ __forceinline__ void short_rows(const SpmmParams &P, long sb, long n_list, int g,
                                            int lane) {
   constexpr int V = RowShape<D>::V;
@@ -1077,10 +1144,10 @@ __device__ __forceinline__ void short_rows(const SpmmParams &P, long sb, long n_
     float4 accB[V];
 #pragma unroll
     for (int k = 0; k < V; ++k) accB[k] = make_float4(0.f, 0.f, 0.f, 0.f);
-    gather_pair<D, WMODE, MASKED, TAG>(P, ser[0] ? 0 : eb[0], ser[0] ? 0 : ee[0],
-                                  ser[1] ? 0 : eb[1], ser[1] ? 0 : ee[1], lane, acc, accB);
-    if (rr[0] >= 0 && !ser[0]) epilogue<D>(P, (int)rr[0], lane, acc);
-    if (rr[1] >= 0 && !ser[1]) epilogue<D>(P, (int)rr[1], lane, accB);
+    gather_pair<D, WMODE, MASKED, TAG, BF>(P, ser[0] ? 0 : eb[0], ser[0] ? 0 : ee[0],
+                                      ser[1] ? 0 : eb[1], ser[1] ? 0 : ee[1], lane, acc, accB);
+    if (rr[0] >= 0 && !ser[0]) epilogue<D, BF>(P, (int)rr[0], lane, acc);
+    if (rr[1] >= 0 && !ser[1]) epilogue<D, BF>(P, (int)rr[1], lane, accB);
     if (ser[0] || ser[1]) {
 #pragma unroll 1
       for (int h = 0; h < 2; ++h) {
@@ -1131,12 +1198,13 @@ __device__ __forceinline__ void short_rows(const SpmmParams &P, long sb, long n_
     if (!serial_long<D, BITS>(P, ee - eb)) return;  // owned by chunk blocks
     chunk_row_serial<D, WMODE>(P, eb, ee, lane, acc);
   } else {
-    gather_row<D, WMODE, MASKED, BITS, TAG>(P, eb, ee, lane, acc);
+    gather_row<D, WMODE, MASKED, BITS, TAG, BF>(P, eb, ee, lane, acc);
   }
-  epilogue<D>(P, (int)row, lane, acc);
+  epilogue<D, BF>(P, (int)row, lane, acc);
 }
 
-template <int D, int WMODE, bool MASKED, bool PAIR, bool BITS = false, int TAG = TAG_NONE>
+template <int D, int WMODE, bool MASKED, bool PAIR, bool BITS = false, int TAG = TAG_NONE,
+          bool BF = false>
 __device__ __forceinline__ void spmm_body(const SpmmParams &P) {
   constexpr int V = RowShape<D>::V;
   __shared__ float4 red[16 * (D / 4)];
@@ -1156,18 +1224,18 @@ __device__ __forceinline__ void spmm_body(const SpmmParams &P) {
     const int per = (((len + 15) >> 4) + 15) & ~15;  // multiple of 16
     const int gb = ch.y + g * per;
     const int ge = min(ch.z, gb + per);
-    if (gb < ge) gather_row<D, WMODE, MASKED, BITS, TAG>(P, gb, ge, lane, acc);
+    if (gb < ge) gather_row<D, WMODE, MASKED, BITS, TAG, BF>(P, gb, ge, lane, acc);
     block_reduce16<D>(red, g, lane, acc);
     if (ch.w < 0) {   // the row's only chunk
       if (g == 0 && lane < RowShape<D>::LANES) {
         float4 T[V];
 #pragma unroll
         for (int k = 0; k < V; ++k) T[k] = red[lane + 16 * k];
-        epilogue<D>(P, ch.x, lane, T);
+        epilogue<D, BF>(P, ch.x, lane, T);
       }
       return;
     }
-    split_row_arrive<D>(P, ch, red, g, lane);
+    split_row_arrive<D, BF>(P, ch, red, g, lane);
     return;
   }
   const long sb = (long)blockIdx.x - P.n_chunks;
@@ -1175,7 +1243,7 @@ __device__ __forceinline__ void spmm_body(const SpmmParams &P) {
   // list length in device memory (a list built on the stream, e.g. inside a
   // captured step; n_row_list is its capacity): workgroups past it exit
   if (MASKED && P.row_list && P.row_count) n = min(n, *P.row_count);
-  short_rows<D, WMODE, MASKED, PAIR, BITS, TAG>(P, sb, n, g, lane);
+  short_rows<D, WMODE, MASKED, PAIR, BITS, TAG, BF>(P, sb, n, g, lane);
 }
 
 // Full-CSR launches (the roofline kernel) and masked / row-list launches are
@@ -1255,6 +1323,66 @@ template <int D, int WMODE>
 __global__ __launch_bounds__(256) BBGR_WAVES(Tune<D>::pair_waves) void spmm_adam_pair_kernel(
     SpmmParams P) {
   spmm_body<D, WMODE, false, true>(P);
+}
+
+// bf16 source / y tables (bbgr_spmm_bf16: the forward chain's launches). The
+// bodies above with BF set: 8-byte gathers per lane, fp32 sums in the fp32
+// kernels' order, y rounded once. Symbols of their own, so the fp32 kernels
+// keep their code and register budgets; occupancy is the compiler's choice
+// (the 8-byte loads hold half the registers of the fp32 forms' batches).
+template <int D, int WMODE>
+__global__ __launch_bounds__(256) void spmm_bf16_kernel(SpmmParams P) {
+  spmm_body<D, WMODE, false, false, false, TAG_NONE, true>(P);
+}
+
+template <int D, int WMODE>
+__global__ __launch_bounds__(256) void spmm_bf16_pair_kernel(SpmmParams P) {
+  spmm_body<D, WMODE, false, true, false, TAG_NONE, true>(P);
+}
+
+template <int D, int WMODE>
+__global__ __launch_bounds__(256) void spmm_bf16_masked_kernel(SpmmParams P) {
+  spmm_body<D, WMODE, true, false, false, TAG_NONE, true>(P);
+}
+
+template <int D, int WMODE>
+__global__ __launch_bounds__(256) void spmm_bf16_masked_pair_kernel(SpmmParams P) {
+  spmm_body<D, WMODE, true, true, false, TAG_NONE, true>(P);
+}
+
+template <int D, int WMODE>
+static int launch_spmm_bf16(const SpmmParams &P, hipStream_t st) {
+  const bool masked = P.row_mask || P.row_list;
+  const long short_rows = P.row_list ? P.n_row_list : (long)(P.row_end - P.row_begin);
+  const long short_blocks = P.pair_rows ? (short_rows + 31) / 32 : (short_rows + 15) / 16;
+  const long grid = (long)P.n_chunks + short_blocks;
+  if (grid <= 0) return BBGR_OK;
+  const dim3 gd((unsigned)grid), bd(256);
+  if (P.pair_rows) {
+    if (masked) hipLaunchKernelGGL((spmm_bf16_masked_pair_kernel<D, WMODE>), gd, bd, 0, st, P);
+    else hipLaunchKernelGGL((spmm_bf16_pair_kernel<D, WMODE>), gd, bd, 0, st, P);
+  } else {
+    if (masked) hipLaunchKernelGGL((spmm_bf16_masked_kernel<D, WMODE>), gd, bd, 0, st, P);
+    else hipLaunchKernelGGL((spmm_bf16_kernel<D, WMODE>), gd, bd, 0, st, P);
+  }
+  BBGR_LAUNCHED("spmm_bf16_kernel");
+  return BBGR_OK;
+}
+
+template <int D>
+static int dispatch_bf16(const SpmmParams &P, int wmode, hipStream_t st) {
+  return wmode == 1 ? launch_spmm_bf16<D, 1>(P, st) : launch_spmm_bf16<D, 0>(P, st);
+}
+
+// fp32 table -> bf16 table, 4 columns per thread (16-byte load, 8-byte store)
+__global__ __launch_bounds__(256) void to_bf16_kernel(long n4, int d4, const float *src,
+                                                      long ldsrc, uint16_t *dst, long lddst) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n4) return;
+  const long r = i / d4;
+  const int c = (int)(i - r * d4);
+  const float4 v = ld_nt(reinterpret_cast<const float4 *>(src + r * ldsrc) + c);
+  reinterpret_cast<uint2 *>(dst + r * lddst)[c] = bf16_pack(v);
 }
 
 template <int D>
@@ -1548,6 +1676,125 @@ extern "C" int bbgr_spmm(const bbgr_csr *csr, const bbgr_spmm_args *a,
     case 64: return dispatch_wmode<64>(P, a->weight_mode, n_split, st, tag_read);
     case 128: return dispatch_wmode<128>(P, a->weight_mode, n_split, st, tag_read);
     default: return dispatch_wmode<256>(P, a->weight_mode, n_split, st, tag_read);
+  }
+}
+
+extern "C" int bbgr_to_bf16(int64_t n_rows, int32_t d, const float *src, int64_t ldsrc,
+                            uint16_t *dst, int64_t lddst, bbgr_stream_t stream) {
+  BBGR_REQUIRE(n_rows >= 0 && d > 0 && (d & 3) == 0, "bbgr_to_bf16: n_rows >= 0, d a multiple of 4");
+  if (n_rows == 0) return BBGR_OK;
+  BBGR_REQUIRE(src && dst, "bbgr_to_bf16: null src / dst");
+  BBGR_REQUIRE(aligned16(src) && ldsrc >= d && (ldsrc & 3) == 0,
+               "bbgr_to_bf16: src must be 16-byte aligned with ldsrc >= d, ldsrc % 4 == 0");
+  BBGR_REQUIRE(aligned16(dst) && lddst >= d && (lddst & 7) == 0,
+               "bbgr_to_bf16: dst must be 16-byte aligned with lddst >= d, lddst % 8 == 0");
+  const long n4 = (long)n_rows * (d / 4);
+  BBGR_REQUIRE((n4 + 255) / 256 <= 0x7fffffffL, "bbgr_to_bf16: table too large for one launch");
+  hipLaunchKernelGGL(to_bf16_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0,
+                     as_stream(stream), n4, d / 4, src, (long)ldsrc, dst, (long)lddst);
+  BBGR_LAUNCHED("to_bf16_kernel");
+  return BBGR_OK;
+}
+
+#define BBGR_BF16_UNSUPPORTED(cond, msg) \
+  do {                                   \
+    if (cond) {                          \
+      set_error("%s", msg);              \
+      return BBGR_ERR_UNSUPPORTED;       \
+    }                                    \
+  } while (0)
+
+extern "C" int bbgr_spmm_bf16(const bbgr_csr *csr, const bbgr_spmm_args *a,
+                              const bbgr_spmm_bf16_io *h, bbgr_stream_t stream) {
+  BBGR_REQUIRE(csr && a && h, "bbgr_spmm_bf16: null csr/args/io");
+  BBGR_REQUIRE(csr->n_rows >= 0 && csr->n_cols >= 0 && csr->nnz >= 0,
+               "bbgr_spmm_bf16: negative csr size");
+  BBGR_REQUIRE(csr->indptr && (csr->nnz == 0 || csr->indices),
+               "bbgr_spmm_bf16: null csr arrays");
+  const int d = a->d;
+  if (d != 64 && d != 128 && d != 256) {
+    set_error("bbgr_spmm_bf16: embedding dim %d unsupported (64, 128, 256)", d);
+    return BBGR_ERR_UNSUPPORTED;
+  }
+  BBGR_REQUIRE(!a->x && !a->y, "bbgr_spmm_bf16: args x / y must be NULL (the io struct replaces them)");
+  // the subset forward_steps issues; everything else is bbgr_spmm's
+  BBGR_BF16_UNSUPPORTED(a->weight_mode == 2, "bbgr_spmm_bf16: weight_mode 2 unsupported (0 or 1)");
+  BBGR_BF16_UNSUPPORTED(a->add, "bbgr_spmm_bf16: add unsupported");
+  BBGR_BF16_UNSUPPORTED(a->adam_param || a->adam_grad || a->adam_mirror,
+                        "bbgr_spmm_bf16: fused Adam (adam_param / adam_grad / adam_mirror) unsupported");
+  BBGR_BF16_UNSUPPORTED(a->src_mask || a->src_mask_bits,
+                        "bbgr_spmm_bf16: src_mask / src_mask_bits unsupported");
+  BBGR_BF16_UNSUPPORTED(a->src_bits, "bbgr_spmm_bf16: src_bits unsupported");
+  BBGR_BF16_UNSUPPORTED(a->src_tagged || a->tag_out,
+                        "bbgr_spmm_bf16: src_tagged / tag_out unsupported");
+  BBGR_BF16_UNSUPPORTED(a->y_map || a->acc_map || a->add_map || a->acc_in_map || a->adam_map,
+                        "bbgr_spmm_bf16: row maps (y_map / acc_map / add_map / acc_in_map) unsupported");
+  BBGR_BF16_UNSUPPORTED(a->use_range, "bbgr_spmm_bf16: use_range unsupported");
+  BBGR_REQUIRE(a->weight_mode == 0 || a->weight_mode == 1,
+               "bbgr_spmm_bf16: weight_mode not in {0,1}");
+  BBGR_REQUIRE(h->x || csr->nnz == 0, "bbgr_spmm_bf16: null x");
+  BBGR_REQUIRE(!h->x || aligned16(h->x), "bbgr_spmm_bf16: x must be 16-byte aligned");
+  BBGR_REQUIRE(!h->x || (h->ldx >= d && (h->ldx & 7) == 0),
+               "bbgr_spmm_bf16: ldx must be >= d and a multiple of 8");
+  BBGR_REQUIRE(!h->y || aligned16(h->y), "bbgr_spmm_bf16: y must be 16-byte aligned");
+  BBGR_REQUIRE(!h->y || (h->ldy >= d && (h->ldy & 7) == 0),
+               "bbgr_spmm_bf16: ldy must be >= d and a multiple of 8");
+  BBGR_REQUIRE(ld_ok(a->acc_in, a->ldacc_in, d) && ld_ok(a->acc_out, a->ldacc_out, d),
+               "bbgr_spmm_bf16: acc tables must be 16-byte aligned with ld >= d, ld % 4 == 0");
+  BBGR_REQUIRE(a->weight_mode != 1 || a->edge_val, "bbgr_spmm_bf16: weight_mode 1 needs edge_val");
+  BBGR_REQUIRE(csr->n_chunks == 0 || csr->chunks, "bbgr_spmm_bf16: plan chunks missing");
+  BBGR_REQUIRE(csr->n_split == 0 || (csr->split && a->partial),
+               "bbgr_spmm_bf16: split rows need plan + partial workspace");
+  BBGR_REQUIRE(csr->n_chunks == 0 || csr->long_threshold > 0,
+               "bbgr_spmm_bf16: plan without long_threshold");
+  BBGR_REQUIRE(!a->row_count || a->row_list, "bbgr_spmm_bf16: row_count needs row_list");
+  BBGR_REQUIRE(!a->row_list || a->n_row_list >= 0, "bbgr_spmm_bf16: negative n_row_list");
+  BBGR_REQUIRE(!a->row_list || a->row_mask || csr->n_chunks == 0,
+               "bbgr_spmm_bf16: row_list needs row_mask when the plan has long-row chunks");
+
+  SpmmParams P = {};
+  P.n_rows = csr->n_rows;
+  P.long_threshold = csr->n_chunks ? csr->long_threshold : 0x7fffffff;
+  P.n_chunks = csr->n_chunks;
+  P.indptr = csr->indptr;
+  P.indices = csr->indices;
+  P.chunks = reinterpret_cast<const int4 *>(csr->chunks);
+  P.split = reinterpret_cast<const int4 *>(csr->split);
+  // the 2-byte tables' addresses ride in the fp32 fields (RowVec / src_row)
+  P.x = reinterpret_cast<const float *>(h->x);
+  P.ldx = h->ldx;
+  P.y = reinterpret_cast<float *>(h->y);
+  P.ldy = h->ldy;
+  P.edge_val = a->edge_val;
+  P.y_scale = a->y_scale;
+  P.y_scale_s = a->y_scale_s;
+  P.acc_in = a->acc_in;
+  P.ldacc_in = a->ldacc_in;
+  P.acc_out = a->acc_out;
+  P.ldacc_out = a->ldacc_out;
+  P.acc_scale = a->acc_scale;
+  P.acc_scale_s = a->acc_scale_s;
+  P.gamma = a->gamma;
+  P.acc_mask = a->acc_mask;
+  P.partial = a->partial;
+  P.chunk_edges = csr->chunk_edges > 0 ? csr->chunk_edges : 2048;
+  P.arrivals = a->partial ? reinterpret_cast<int *>(a->partial + (long)csr->n_chunks * d)
+                          : nullptr;
+  P.row_mask = a->row_mask;
+  P.row_list = (const long *)a->row_list;
+  P.n_row_list = a->n_row_list;
+  P.row_count = (const long *)a->row_count;
+  P.row_begin = 0;
+  P.row_end = csr->n_rows;
+  P.chunk_begin = 0;
+  P.pair_rows = pair_rows(csr);
+  P.nt_from = a->stream_from > 0 ? a->stream_from : 0x7fffffff;
+  P.nt_out_from = a->stream_out_from > 0 ? a->stream_out_from : 0x7fffffff;
+  hipStream_t st = as_stream(stream);
+  switch (d) {
+    case 64: return dispatch_bf16<64>(P, a->weight_mode, st);
+    case 128: return dispatch_bf16<128>(P, a->weight_mode, st);
+    default: return dispatch_bf16<256>(P, a->weight_mode, st);
   }
 }
 

@@ -469,7 +469,7 @@ class ShardedTrainer(FusedTrainer):
                  sparse_exchange: bool = True, vertex_order: str = "input",
                  frontier_parts: int = 2, native_comm: bool = False,
                  overlap_item_adam: bool | None = None, column_chains: int = 1,
-                 own_items: bool = True):
+                 own_items: bool = True, forward_dtype: str = "fp32"):
         """local_edges: int32 [2, E_local] with LOCAL user ids; cred / u0: rows of
         this rank's users; i0: the full (replicated) item table; batch_size:
         users per step on THIS rank. vertex_order="degree": local users by
@@ -478,7 +478,10 @@ class ShardedTrainer(FusedTrainer):
         d/C-column slices of the tables, each on its own stream, their issue
         interleaved one exchange at a time (_interleave), so one chain's SpMMs
         overlap the other's item all-reduces. own_items: item rows owned by
-        ranks (module docstring; GS fused only)."""
+        ranks (module docstring; GS fused only). forward_dtype: "fp32" only (the
+        item exchange sums fp32 partial rows; the bf16 forward is single-GPU)."""
+        if forward_dtype != "fp32":
+            raise ValueError("ShardedTrainer takes forward_dtype='fp32' only")
         _lib.require_gpu()
         if variant not in VARIANTS:
             raise ValueError(f"unknown variant {variant!r}")

@@ -185,31 +185,32 @@ class Csr:
         cache[key] = out
         return out
 
-    def stream_from(self, d: int) -> int:
+    def stream_from(self, d: int, elem_bytes: int = 4) -> int:
         """bbgr_spmm_args.stream_from for a gather of d-wide source rows: 0
         unless the columns are in descending-degree order (BipartiteGraph with
-        vertex_order="degree"); then the hot prefix of the source table."""
+        vertex_order="degree"); then the hot prefix of the source table.
+        `elem_bytes`: 4 (fp32 tables) or 2 (bf16 tables: twice the rows fit)."""
         if not self.__dict__.get("cols_by_degree", False):
             return 0
         hot = self.__dict__.get("hot_bytes", HOT_BYTES)
-        if self.n_cols * 4 * d <= hot:   # the whole table stays cached (C1, C2)
+        if self.n_cols * elem_bytes * d <= hot:   # the whole table stays cached (C1, C2)
             return 0
-        return max(1, min(self.n_cols // 8, hot // (4 * d)))
+        return max(1, min(self.n_cols // 8, hot // (elem_bytes * d)))
 
-    def stream_out_from(self, d: int) -> int:
+    def stream_out_from(self, d: int, elem_bytes: int = 4) -> int:
         """bbgr_spmm_args.stream_out_from for d-wide output rows: 0 unless the
         rows are in descending-degree order; then the hot prefix of the output
         table (the next product gathers it)."""
         if not self.__dict__.get("rows_by_degree", False):
             return 0
         hot = self.__dict__.get("hot_bytes", HOT_BYTES)
-        if self.n_rows * 4 * d <= hot:
+        if self.n_rows * elem_bytes * d <= hot:
             return 0
         if OUT_POLICY == "nt":      # A/B: every output row streamed
             return 1
         if OUT_POLICY == "none":    # A/B: every output row default policy
             return 0
-        return max(1, min(self.n_rows // 8, hot // (4 * d)))
+        return max(1, min(self.n_rows // 8, hot // (elem_bytes * d)))
 
     def partial_workspace(self, d: int) -> torch.Tensor | None:
         """bbgr_spmm_args.partial: n_chunks*d floats of chunk partials, then

@@ -205,6 +205,7 @@ class SpmmTimer:
         """{(rows, nnz, d): (launches, total ms)} over one kind of launch:
         "full" (spmm_kernel), "masked" (frontier masks / row lists,
         spmm_masked_kernel) or "adam" (fused Adam epilogue, spmm_adam_kernel);
+        launches over bf16 tables are "full_bf16" / "masked_bf16";
         `table_rows` keeps only launches over a CSR with that many rows (the
         item-row CSR: the item<-user products)."""
         torch.cuda.synchronize()
@@ -379,7 +380,18 @@ def spmm(prod: Product, x: torch.Tensor, first: bool, *, y=None, y_scale=None,
     instead of loading src_mask per edge (bbgr_spmm_args.tag_out /
     src_tagged; bitwise the src_mask launch). `src_mask_bits` (with src_mask):
     the same mask packed one bit per row (bbgr_mask_pack), read by the
-    per-edge test instead of the bytes (bbgr_spmm_args.src_mask_bits)."""
+    per-edge test instead of the bytes (bbgr_spmm_args.src_mask_bits).
+    A torch.bfloat16 `x` routes to bbgr_spmm_bf16 (the forward chain's subset:
+    d in {64, 128, 256}, y bf16 or None, the fp32 accumulator fields, row_mask,
+    row_list / row_count, acc_mask); anything that entry refuses raises
+    ValueError here. Its fp32 outputs are bitwise this function's on x.float()."""
+    bf16 = x.dtype == torch.bfloat16
+    if bf16:
+        _check_bf16(prod, x, y, add=add, adam=adam, src_mask=src_mask, src_bits=src_bits,
+                    src_mask_bits=src_mask_bits, tagged=tagged, tag_out=tag_out, y_map=y_map,
+                    acc_map=acc_map, add_map=add_map, src_input=src_input or None, rng=rng)
+    elif y is not None and y.dtype == torch.bfloat16:
+        raise ValueError("spmm: a bf16 y needs a bf16 x")
     listed_on_device = row_count is not None
     if isinstance(row_count, ListLength):
         n = row_count.length()
@@ -430,33 +442,73 @@ def spmm(prod: Product, x: torch.Tensor, first: bool, *, y=None, y_scale=None,
     if src_mask_bits is not None and a.src_mask:
         a.src_mask_bits = ptr(src_mask_bits)
     # input-order source rows carry no hot prefix; mapped output rows neither
-    a.stream_from = 0 if src_input else prod.csr.stream_from(d)
-    a.stream_out_from = 0 if y_map is not None else prod.csr.stream_out_from(d)
+    # (bf16 tables: the same byte budget holds twice the rows)
+    eb = 2 if bf16 else 4
+    a.stream_from = 0 if src_input else prod.csr.stream_from(d, eb)
+    a.stream_out_from = 0 if y_map is not None else prod.csr.stream_out_from(d, eb)
     cs = prod.input_struct() if src_input else prod.csr._struct
+    if bf16:   # the 2-byte tables travel in their own struct; args x / y stay NULL
+        io = _lib.SpmmBf16Io(ptr(x), ld(x), ptr(y), ld(y))
+        a.x, a.ldx, a.y, a.ldy = None, 0, None, 0
+
+        def launch():
+            call("bbgr_spmm_bf16", ctypes.byref(cs), ctypes.byref(a), ctypes.byref(io),
+                 stream_handle())
+    else:
+        def launch():
+            call("bbgr_spmm", ctypes.byref(cs), ctypes.byref(a), stream_handle())
     if _timer is None:
-        call("bbgr_spmm", ctypes.byref(cs), ctypes.byref(a), stream_handle())
+        launch()
         return
     masked = src_mask is not None or row_mask is not None or row_list is not None
     kind = "masked" if masked else ("full" if adam is None else
                                     "adam" if adam.grad is None else "adam_side")
+    if bf16:   # kinds of their own: "full_bf16" / "masked_bf16"
+        kind += "_bf16"
     if _timer.select is not None and not _timer.select(kind, prod):
-        call("bbgr_spmm", ctypes.byref(cs), ctypes.byref(a), stream_handle())
+        launch()
         return
     if listed_on_device:   # the list is row_mask's rows, built on the stream
         row_list = None
     if _timer.count:
-        call("bbgr_spmm", ctypes.byref(cs), ctypes.byref(a), stream_handle())
+        launch()
         _timer.count_launch(prod, kind, d, rng, src_mask, row_mask, row_list, src_input)
         return
     ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     ev0.record()
-    call("bbgr_spmm", ctypes.byref(cs), ctypes.byref(a), stream_handle())
+    launch()
     ev1.record()
     rows, nnz = prod.csr.n_rows, prod.csr.nnz
     if rng is not None and row_list is None:   # a row range: its own rows and edges
         rows, nnz = rng[1] - rng[0], prod.csr.range_nnz(rng[0], rng[1])
     _timer.records.append((rows, nnz, d, kind, ev0, ev1, prod.csr.n_rows, prod.csr.n_cols,
                            mask_signature(src_mask, row_mask, row_list)))
+
+
+def _check_bf16(prod: Product, x, y, **unsupported) -> None:
+    """ValueError for whatever bbgr_spmm_bf16 would refuse."""
+    d = x.shape[1]
+    if d not in (64, 128, 256):
+        raise ValueError(f"spmm: bf16 tables need d in (64, 128, 256), got {d}")
+    if y is not None and y.dtype != torch.bfloat16:
+        raise ValueError(f"spmm: a bf16 x writes a bf16 y, got {y.dtype}")
+    for name, t in (("x", x), ("y", y)):
+        if t is not None and (t.data_ptr() % 16 or ld(t) % 8):
+            raise ValueError(f"spmm: bf16 {name} must be 16-byte aligned with a row stride "
+                             "that is a multiple of 8 elements")
+    bad = [k for k, v in unsupported.items() if v is not None]
+    if bad:
+        raise ValueError("spmm: bf16 tables do not take " + ", ".join(sorted(bad)))
+
+
+def to_bf16(src: torch.Tensor, dst: torch.Tensor) -> torch.Tensor:
+    """dst = src rounded to bf16, nearest even (bbgr_to_bf16), on the current
+    stream. src fp32 [n, d], dst bf16 [n, d]."""
+    if src.dtype != torch.float32 or dst.dtype != torch.bfloat16 or src.shape != dst.shape:
+        raise ValueError("to_bf16: fp32 source and bf16 destination of the same shape")
+    call("bbgr_to_bf16", src.shape[0], src.shape[1], ptr(src), ld(src), ptr(dst), ld(dst),
+         stream_handle())
+    return dst
 
 
 def epilogue(t: torch.Tensor, *, y=None, y_scale=None, y_scale_s: float = 1.0, add=None,
@@ -523,15 +575,16 @@ def _check_table(name, t, rows, d=None):
         raise ValueError(f"{name} must have unit column stride")
 
 
-def _buffers(ws: dict | None, device, d: int):
-    """Allocator for the chain's intermediate tables; reuses ws[(tag, rows, d)]."""
+def _buffers(ws: dict | None, device, d: int, dtype=torch.float32):
+    """Allocator for the chain's intermediate tables; reuses ws[(tag, rows, d)]
+    (bf16 tables: ws[(tag, rows, d, dtype)])."""
     def new(tag: str, n: int) -> torch.Tensor:
         if ws is None:
-            return torch.empty(n, d, dtype=torch.float32, device=device)
-        key = (tag, n, d)
+            return torch.empty(n, d, dtype=dtype, device=device)
+        key = (tag, n, d) if dtype == torch.float32 else (tag, n, d, dtype)
         t = ws.get(key)
         if t is None:
-            t = ws[key] = torch.empty(n, d, dtype=torch.float32, device=device)
+            t = ws[key] = torch.empty(n, d, dtype=dtype, device=device)
         return t
     return new
 
@@ -548,7 +601,7 @@ def drain(steps):
 def forward_steps(pair: OperatorPair, u0: torch.Tensor, i0: torch.Tensor, num_layers: int,
                   order: str = ORDER_GS, out_u: torch.Tensor | None = None,
                   out_i: torch.Tensor | None = None, ws: dict | None = None, reduce=None,
-                  final_rows=None, tag=None):
+                  final_rows=None, tag=None, table_dtype=torch.float32):
     """Final (layer-mean) user and item tables. u0 [U,d], i0 [I,d] fp32.
     A generator: it yields after issuing each item-row product (with `reduce`,
     each exchange point), so the caller can interleave the issue of several
@@ -568,11 +621,24 @@ def forward_steps(pair: OperatorPair, u0: torch.Tensor, i0: torch.Tensor, num_la
     rows only (item_mask must cover them).
     `tag=(tag_out, tag_mask)` (GS, K >= 2): the first user product, a full
     launch, also writes the user CSR's column indices tagged with tag_mask
-    (bit 31 = dead item) for backward_steps(tagged=...)."""
+    (bit 31 = dead item) for backward_steps(tagged=...).
+    `table_dtype=torch.bfloat16` (d >= 64; no `reduce`, input-order pair or
+    `tag`): the tables the products gather are bf16. The ego tables are
+    rounded into workspace shadows before the first product (GS: u0; Jacobi:
+    u0 and i0) and every fed-forward layer table is written in bf16, rounded
+    once from its fp32 value; the row sums, the layer-mean accumulators (which
+    start from the fp32 u0 / i0) and the outputs stay fp32."""
     U, I = pair.num_users, pair.num_items
     d = u0.shape[1]
     _check_table("user table", u0, U, d)
     _check_table("item table", i0, I, d)
+    if table_dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"table_dtype must be torch.float32 or torch.bfloat16, got {table_dtype}")
+    bf16 = table_dtype == torch.bfloat16
+    if bf16 and (reduce is not None or pair.io is not None or tag is not None):
+        raise ValueError("bf16 tables take no reduce hook, input-order pair or tag")
+    if bf16 and d not in (64, 128, 256):
+        raise ValueError(f"bf16 tables need an embedding width of 64, 128 or 256, got {d}")
     acc_u = torch.empty_like(u0, memory_format=torch.contiguous_format) if out_u is None else out_u
     acc_i = torch.empty_like(i0, memory_format=torch.contiguous_format) if out_i is None else out_i
     K = int(num_layers)
@@ -594,15 +660,18 @@ def forward_steps(pair: OperatorPair, u0: torch.Tensor, i0: torch.Tensor, num_la
     # epilogue places them through the side's map; the first products gather
     # the input-order u0 / i0 through input-id column indices
     am_u, am_i = (io.user_map, io.item_map) if io is not None else (None, None)
+    newt = _buffers(ws, u0.device, d, table_dtype)   # the gathered tables
+    # the first products' sources: the ego tables, or their bf16 shadows
+    su0 = to_bf16(u0, newt("u0h", U)) if bf16 else u0
     if order == ORDER_GS:
-        bufU, bufI = new("u0", U), new("i0", I)
+        bufU, bufI = newt("u0", U), newt("i0", I)
         il = {}
         if ilist is not None and reduce is None and mi is not None:
             il = dict(row_list=ilist[0], row_count=ilist[1])
         for k in range(1, K + 1):
             g = gl if k == K else 1.0
             last = k == K
-            _item_product(FI, u0 if k == 1 else bufU, k == 1, reduce, new, y=bufI,
+            _item_product(FI, su0 if k == 1 else bufU, k == 1, reduce, new, y=bufI,
                           y_scale=pair.feed_fwd_iu, acc_in=i0 if k == 1 else acc_i,
                           acc_out=acc_i, acc_scale=FI.out_scale, gamma=g,
                           row_mask=mi if last else None, acc_mask=ami, acc_map=am_i,
@@ -616,19 +685,20 @@ def forward_steps(pair: OperatorPair, u0: torch.Tensor, i0: torch.Tensor, num_la
                  acc_scale=FU.out_scale, gamma=g, row_mask=mu if last else None,
                  acc_mask=mu, row_list=ulist if last else None, acc_map=am_u, **tk)
     elif order == ORDER_J:
-        bufU, bufI = [new("u0", U), new("u1", U)], [new("i0", I), new("i1", I)]
+        bufU, bufI = [newt("u0", U), newt("u1", U)], [newt("i0", I), newt("i1", I)]
+        si0 = to_bf16(i0, newt("i0h", I)) if bf16 else i0
         cur = 0
         for k in range(1, K + 1):
             g = gl if k == K else 1.0
             nxt = 1 - cur
             last = k == K
-            _item_product(FI, u0 if k == 1 else bufU[cur], k == 1, reduce, new,
+            _item_product(FI, su0 if k == 1 else bufU[cur], k == 1, reduce, new,
                           y=bufI[nxt] if k < K else None, y_scale=pair.feed_fwd_iu,
                           acc_in=i0 if k == 1 else acc_i, acc_out=acc_i,
                           acc_scale=FI.out_scale, gamma=g, row_mask=mi if last else None,
                           acc_mask=ami, acc_map=am_i, src_input=io is not None and k == 1)
             yield
-            spmm(FU, i0 if k == 1 else bufI[cur], k == 1,
+            spmm(FU, si0 if k == 1 else bufI[cur], k == 1,
                  y=bufU[nxt] if k < K else None, y_scale=pair.feed_fwd_ui,
                  acc_in=u0 if k == 1 else acc_u, acc_out=acc_u,
                  acc_scale=FU.out_scale, gamma=g, row_mask=mu if last else None,
@@ -643,10 +713,10 @@ def forward_steps(pair: OperatorPair, u0: torch.Tensor, i0: torch.Tensor, num_la
 def forward(pair: OperatorPair, u0: torch.Tensor, i0: torch.Tensor, num_layers: int,
             order: str = ORDER_GS, out_u: torch.Tensor | None = None,
             out_i: torch.Tensor | None = None, ws: dict | None = None, reduce=None,
-            final_rows=None, tag=None):
+            final_rows=None, tag=None, table_dtype=torch.float32):
     """forward_steps run to completion: the final (u, i) tables."""
     return drain(forward_steps(pair, u0, i0, num_layers, order, out_u, out_i, ws, reduce,
-                               final_rows, tag))
+                               final_rows, tag, table_dtype))
 
 
 def backward_steps(pair: OperatorPair, gU: torch.Tensor, gI: torch.Tensor, num_layers: int,
@@ -819,13 +889,35 @@ def backward(pair: OperatorPair, gU: torch.Tensor, gI: torch.Tensor, num_layers:
 
 
 def propagate(pair: OperatorPair, u0: torch.Tensor, i0: torch.Tensor, num_layers: int,
-              order: str = ORDER_GS):
+              order: str = ORDER_GS, table_dtype=torch.float32):
     """Differentiable (u0, i0) -> (u_final, i_final): the registered operator
     bbgr::propagate (ops.py), whose backward is bbgr::propagate_backward;
     replaces the autograd of the reference's K x torch.sparse.mm +
-    stack().mean() chain."""
+    stack().mean() chain.
+    `table_dtype=torch.bfloat16`: the forward gathers bf16 tables (see
+    forward_steps); the backward is the fp32 chain (it reads no forward
+    activation). That path runs the Python chain under autograd, not the
+    registered C++ operator, which stays fp32 only."""
+    if table_dtype != torch.float32:
+        return _PropagateBf16.apply(u0, i0, pair, int(num_layers), order, table_dtype)
     from . import ops
     return ops.propagate(u0, i0, ops.pair_key(pair), int(num_layers), order)
+
+
+class _PropagateBf16(torch.autograd.Function):
+    """propagate() with reduced-precision forward tables."""
+
+    @staticmethod
+    def forward(ctx, u0, i0, pair, K, order, table_dtype):
+        _lib.require_gpu(u0)
+        ctx.pair, ctx.K, ctx.order = pair, K, order
+        return forward(pair, u0.contiguous(), i0.contiguous(), K, order,
+                       table_dtype=table_dtype)
+
+    @staticmethod
+    def backward(ctx, gU, gI):
+        gu, gi = backward(ctx.pair, gU.contiguous(), gI.contiguous(), ctx.K, ctx.order)
+        return gu, gi, None, None, None, None
 
 
 def propagate_rows(pair: OperatorPair, u0: torch.Tensor, i0: torch.Tensor, num_layers: int,

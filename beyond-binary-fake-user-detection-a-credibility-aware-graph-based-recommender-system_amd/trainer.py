@@ -56,13 +56,31 @@ def resolve_frontier(frontier, nnz: int) -> bool:
     return bool(frontier)
 
 
+FORWARD_DTYPES = {"fp32": torch.float32, "bf16": torch.bfloat16}
+
+
 class FusedTrainer:
+    # forward_dtype="bf16" (opt-in, emb_dim >= 64): the tables the forward
+    # products gather are bf16 (propagate.forward_steps(table_dtype=...)): a
+    # shadow of the user weights (Jacobi: and of the item weights), rounded
+    # from the fp32 masters by a conversion pass at the start of every
+    # forward, and the fed-forward layer tables. The masters, the layer-mean
+    # accumulators, the final tables, BPR, the backward, Adam and the frontier
+    # bookkeeping are the fp32 step's. The default "fp32" is that step, bit
+    # for bit.
+    forward_dtype, table_dtype = "fp32", torch.float32
+
     def __init__(self, graph: BipartiteGraph, variant: str = "v2_pop", cred=None,
                  emb_dim: int = 64, num_layers: int = 3, lr: float = 1e-3,
                  reg: float = 1e-4, batch_size: int = 4096, neg_mix_pop: float | None = None,
                  neg_pop_gamma: float = 0.75, neg_max_tries: int = 50,
                  lambda_fair: float = 0.0, seed: int = 42, u0=None, i0=None,
-                 frontier="auto", fuse_adam: bool = True):
+                 frontier="auto", fuse_adam: bool = True, forward_dtype: str = "fp32"):
+        if forward_dtype not in FORWARD_DTYPES:
+            raise ValueError(f"forward_dtype must be 'fp32' or 'bf16', got {forward_dtype!r}")
+        if forward_dtype == "bf16" and emb_dim < 64:
+            raise ValueError(f"forward_dtype='bf16' needs emb_dim >= 64, got {emb_dim}")
+        self.forward_dtype, self.table_dtype = forward_dtype, FORWARD_DTYPES[forward_dtype]
         _lib.require_gpu()
         if variant not in VARIANTS:
             raise ValueError(f"unknown variant {variant!r}; one of {sorted(VARIANTS)}")
@@ -162,6 +180,7 @@ class FusedTrainer:
         self.tagged = None
         uc = graph.user_csr
         if (self.frontier and order == ORDER_GS and num_layers >= 2 and emb_dim >= 64
+                and forward_dtype == "fp32"   # (the bf16 products write no tagged copy)
                 and uc.nnz <= 24 * uc.n_rows and os.environ.get("BBGR_TAGGED", "0") == "1"):
             self.tagged = torch.empty(max(uc.nnz, 1), dtype=torch.int32, device=dev)
         # Frontier: the item mask also packed one bit per item after the
@@ -250,7 +269,7 @@ class FusedTrainer:
                 out_i=self.itf, ws=self.ws,
                 final_rows=None if masks is None else
                 (masks[0], masks[1], users if listed else None, self._flist(masks)),
-                tag=self._tag(masks))
+                tag=self._tag(masks), table_dtype=self.table_dtype)
         # (a caller's batch may repeat a user: its last user layer then runs on
         # the de-duplicated mask instead of a row list, whose repeated rows
         # would update the in-place accumulator twice)
@@ -503,8 +522,16 @@ class FusedTrainer:
     def forward(self):
         """Final (layer-mean) tables, rows by input id."""
         uf, itf = forward(self.pair, self.user_w, self.item_w, self.K, self.order,
-                          out_u=self.uf, out_i=self.itf, ws=self.ws)
+                          out_u=self.uf, out_i=self.itf, ws=self.ws,
+                          table_dtype=self.table_dtype)
         return _input_rows(self.graph.user_order, uf), _input_rows(self.graph.item_order, itf)
+
+    def forward_shadow(self):
+        """The bf16 shadows the last forward gathered its first products from:
+        (user, item) in the graph's row order; item is None in GS order (only
+        u0 is gathered there), both None with forward_dtype="fp32"."""
+        bf = torch.bfloat16
+        return (self.ws.get(("u0h", self.U, self.d, bf)), self.ws.get(("i0h", self.I, self.d, bf)))
 
     def _train_rows(self) -> Csr:
         """The graph's user -> item rows by INPUT id (rows and columns), columns
@@ -576,7 +603,7 @@ class GraphedStep:
         self.users = torch.zeros(trainer.B, dtype=torch.int64, device=trainer.device)
         host = (trainer.step_count, trainer.sampler.counter)
         # the graph records the launches of THIS configuration
-        self._captured = (trainer.frontier, trainer.fuse_adam, trainer.B)
+        self._captured = (trainer.frontier, trainer.fuse_adam, trainer.B, trainer.forward_dtype)
         trainer.pair.prepare_graph(trainer.d)   # the graph's own split-row workspaces
         torch.cuda.synchronize()
         self.graph = torch.cuda.CUDAGraph()
@@ -589,9 +616,9 @@ class GraphedStep:
 
     def step(self) -> torch.Tensor:
         tr = self.tr
-        if (tr.frontier, tr.fuse_adam, tr.B) != self._captured:
-            raise RuntimeError("GraphedStep: the trainer's frontier / fuse_adam / batch size "
-                               "changed since capture; build a new GraphedStep")
+        if (tr.frontier, tr.fuse_adam, tr.B, tr.forward_dtype) != self._captured:
+            raise RuntimeError("GraphedStep: the trainer's frontier / fuse_adam / batch size / "
+                               "forward_dtype changed since capture; build a new GraphedStep")
         users = tr.next_users()
         if users.numel() != tr.B:       # short tail of an epoch: eager (same device state)
             return tr._step(users, True)

@@ -398,6 +398,60 @@ int bbgr_epilogue(int32_t n_rows, const float *t, int64_t ldt,
                   const bbgr_spmm_args *args, bbgr_stream_t stream);
 
 /* ------------------------------------------------------------------------- */
+/* bf16 tables for the forward chain (opt-in; an addition to ABI 12)          */
+/*                                                                            */
+/* LightGCN's propagation is linear and its backward reads no forward         */
+/* activation, so the layer tables whose only reader is the next product's    */
+/* gather can be kept in bf16 (2 bytes per element, the upper half of an      */
+/* fp32): the gathers move half the bytes. Sums, the layer-mean accumulators  */
+/* and everything downstream stay fp32.                                       */
+/*                                                                            */
+/* The conversion: dst[r, c] = bf16(src[r, c]) for r < n_rows, c < d, round   */
+/* to nearest even; bit for bit torch's .to(torch.bfloat16) on finite values, */
+/* +-0, subnormals and +-inf; a NaN becomes the quiet NaN 0x7fc0. d is a      */
+/* multiple of 4. src: 16-byte aligned, ldsrc >= d, ldsrc % 4 == 0. dst:      */
+/* 16-byte aligned, lddst >= d, lddst % 8 == 0 (elements); columns past d are */
+/* not written.                                                               */
+/* ------------------------------------------------------------------------- */
+int bbgr_to_bf16(int64_t n_rows, int32_t d, const float *src, int64_t ldsrc,
+                 uint16_t *dst, int64_t lddst, bbgr_stream_t stream);
+
+/* The product on a bf16 source table: io->x [n_cols, ldx] replaces args->x   */
+/* and io->y [n_rows, ldy] (nullable) replaces args->y; args->x and args->y   */
+/* must be NULL. Every other field is read from args with its meaning above.  */
+/*   T_r is accumulated in fp32; y[r] = ys_r * T_r is rounded once (nearest   */
+/*   even) to bf16; acc_out = (acc_in + cs_r * T_r) * gamma stays fp32, with  */
+/*   acc_scale, acc_mask and the streaming stores as above.                   */
+/* Supported subset (the launches of the forward chain):                      */
+/*   d in {64, 128, 256}; weight_mode 0 or 1; y_scale, acc_in / acc_out /     */
+/*   acc_scale / gamma / acc_mask; row_mask; row_list with n_row_list and     */
+/*   row_count; the load-balance plan (long-row chunks, split rows through    */
+/*   the fp32 partial workspace, sized as for the fp32 entry); the two-row    */
+/*   form for CSRs with nnz <= 24 * n_rows; stream_from / stream_out_from     */
+/*   (rows of the 2-byte tables: the same byte budget keeps twice the rows).  */
+/* Refused before any launch: BBGR_ERR_UNSUPPORTED for d < 64, weight_mode 2, */
+/*   add, the fused Adam fields, src_mask, src_mask_bits, src_bits,           */
+/*   src_tagged, tag_out, the row maps and use_range; BBGR_ERR_INVALID for    */
+/*   null tables, a set args->x / args->y, or a misaligned table.             */
+/* Alignment: io->x and io->y are 16-byte aligned, ldx and ldy (in elements)  */
+/*   are >= d and multiples of 8, so every row starts on a 16-byte boundary.  */
+/* Relation to the fp32 entry: every output element is the same fp32 sum in   */
+/*   the same order as that entry computes on the source widened to fp32      */
+/*   (edges in CSR order, chunk and split partials in plan order, the same    */
+/*   multiply / fused-multiply-add sequence in the epilogue). acc_out is      */
+/*   therefore bitwise that entry's acc_out on the widened table, and y is    */
+/*   bitwise that entry's y rounded to bf16.                                  */
+typedef struct {
+  const uint16_t *x;
+  int64_t ldx;
+  uint16_t *y;
+  int64_t ldy;
+} bbgr_spmm_bf16_io;
+
+int bbgr_spmm_bf16(const bbgr_csr *csr, const bbgr_spmm_args *args,
+                   const bbgr_spmm_bf16_io *io, bbgr_stream_t stream);
+
+/* ------------------------------------------------------------------------- */
 /* Fused BPR loss: gather -> dot -> log-sigmoid -> (+reg, +fair) -> grads     */
 /*   Replaces LightGCN.bpr_loss, Version-2/lighgcn_cu_pop.py:495-508          */
 /*   (== lightgcn.py:333-349 with ego offset; lightgcn_cu.py:635-648 adds     */
