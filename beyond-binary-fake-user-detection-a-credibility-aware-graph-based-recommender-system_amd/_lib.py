@@ -179,6 +179,26 @@ class SlasInduceArgs(ctypes.Structure):
     ]
 
 
+class FeatColumns(ctypes.Structure):
+    """bbgr_feat_columns (bbgr_feat_*): the per-record device columns."""
+    _fields_ = [
+        ("n", c_int64), ("n_users", c_int32), ("n_items", c_int32),
+        ("user", c_void_p), ("item", c_void_p), ("rating", c_void_p),
+        ("helpful_vote", c_void_p), ("verified", c_void_p), ("timestamp", c_void_p),
+        ("ts_valid", c_void_p), ("n_tokens", c_void_p), ("n_unique_tokens", c_void_p),
+    ]
+
+
+class FeatUserArgs(ctypes.Structure):
+    """bbgr_feat_user_args (bbgr_feat_users)."""
+    _fields_ = [
+        ("u_indptr", c_void_p), ("u_eid", c_void_p), ("b_indptr", c_void_p),
+        ("b_bucket", c_void_p), ("item_rbar", c_void_p), ("global_avg_len", c_double),
+        ("user_x", c_void_p), ("user_y", c_void_p), ("total_reviews", c_void_p),
+        ("helpful_reviews", c_void_p),
+    ]
+
+
 class Pcg64State(ctypes.Structure):
     """bbgr_pcg64: numpy's PCG64 bit_generator.state (128-bit state and
     increment as two 64-bit halves, the buffered 32-bit output)."""
@@ -323,6 +343,14 @@ _SIGNATURES = {
     "bbgr_mark_ids32": ([c_int64, _P, ctypes.c_uint8, _P, c_int64, _P], c_int32),
     "bbgr_slas_induce": ([ctypes.POINTER(SlasInduceArgs), _P, ctypes.POINTER(c_size_t), _P],
                          c_int32),
+    "bbgr_feat_stats": ([ctypes.POINTER(FeatColumns), _P, _P], c_int32),
+    "bbgr_feat_buckets": ([ctypes.POINTER(FeatColumns), c_int64, c_int64, _P, _P,
+                           ctypes.POINTER(c_int32), _P], c_int32),
+    "bbgr_feat_items": ([ctypes.POINTER(FeatColumns), _P, _P, _P, _P, _P,
+                         ctypes.POINTER(c_size_t), _P], c_int32),
+    "bbgr_feat_users": ([ctypes.POINTER(FeatColumns), ctypes.POINTER(FeatUserArgs), _P,
+                         ctypes.POINTER(c_size_t), _P], c_int32),
+    "bbgr_feat_edges": ([ctypes.POINTER(FeatColumns), _P, c_int64, c_int64, _P, _P], c_int32),
     # blueprint names, thin forms of the entry points above
     "bbgr_spmm_f32": ([ctypes.POINTER(CsrStruct), _P, c_int64, _P, c_int64, c_int32, _P, _P,
                        _P, c_float, _P], c_int32),

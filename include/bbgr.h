@@ -1150,6 +1150,96 @@ int bbgr_slas_induce(const bbgr_slas_induce_args *args, void *workspace,
                      size_t *workspace_bytes, bbgr_stream_t stream);
 
 /* ------------------------------------------------------------------------- */
+/* Review columns -> the credibility graph's tensors (main.py:153-196,        */
+/* :247-373, :423-570): Ru and label, six behavioural features per user, the  */
+/* item features and the edge attributes. Appended; the ABI stays 12.         */
+/*                                                                            */
+/* A record is one review that has a user, an item and a rating. The columns  */
+/* are device arrays of n entries in file order. Ids must lie in [0, n_users) */
+/* and [0, n_items): the caller checks them (bbgr.features does, before any   */
+/* launch). Ratings are finite. Every sum is taken in double in a fixed order */
+/* without float atomics (two calls: the same bits); results are rounded to   */
+/* float once, at the store.                                                  */
+/* ------------------------------------------------------------------------- */
+typedef struct {
+  int64_t n;                       /* records, < 2^31 - 1 */
+  int32_t n_users;                 /* < 2^31 - 1 */
+  int32_t n_items;
+  const int32_t *user;
+  const int32_t *item;
+  const float *rating;
+  const int32_t *helpful_vote;
+  const uint8_t *verified;         /* 0 / non-zero */
+  const int64_t *timestamp;        /* milliseconds */
+  const uint8_t *ts_valid;         /* nullable: every record has a timestamp */
+  const int32_t *n_tokens;         /* L = tokens of title + " " + text */
+  const int32_t *n_unique_tokens;  /* distinct tokens among them */
+} bbgr_feat_columns;
+
+/* stats (DEVICE int64 [4]) = {ts_min, ts_max, records with a timestamp, sum  */
+/* of n_tokens}; with no timestamp at all ts_min = INT64_MAX and ts_max =     */
+/* INT64_MIN. Integer atomics only.                                           */
+int bbgr_feat_stats(const bbgr_feat_columns *c, int64_t *stats, bbgr_stream_t stream);
+
+/* The (row, column) pairs of the bucket CSR: for a record with a timestamp   */
+/* rows[e] = user, cols[e] = floor(timestamp / 86400000) - floor(ts_min /     */
+/* 86400000) (floor division: negative timestamps round down); for one        */
+/* without, rows[e] = n_users (a spare row) and cols[e] = 0. *n_cols (HOST)   */
+/* receives the column count. A CSR build over n_users + 1 rows and *n_cols   */
+/* columns then lists every user's buckets in ascending order. ts_min and     */
+/* ts_max are the values bbgr_feat_stats found. BBGR_ERR_INVALID, naming      */
+/* timestamp, before any launch when the bucket range does not fit int32.     */
+int bbgr_feat_buckets(const bbgr_feat_columns *c, int64_t ts_min, int64_t ts_max,
+                      int32_t *rows, int32_t *cols, int32_t *n_cols, bbgr_stream_t stream);
+
+/* Per item, over the reference-order item rows (i_indptr [n_items + 1],      */
+/* i_eid [n]: record ids, ascending within a row):                            */
+/*   item_x [n_items, 2] = {float(double mean of the raw rating), count}      */
+/*   item_rbar [n_items] = the double mean of ri = clamp(round_half_even(     */
+/*                         rating), 1, 5): what the users' deviation is from  */
+/* An item with no record gets mean 0 and count 0. Size query with            */
+/* workspace == NULL.                                                         */
+int bbgr_feat_items(const bbgr_feat_columns *c, const int32_t *i_indptr, const int32_t *i_eid,
+                    float *item_x, double *item_rbar, void *workspace,
+                    size_t *workspace_bytes, bbgr_stream_t stream);
+
+/* Per user, over the reference-order user rows and the bucket CSR's rows:    */
+/*   total_reviews = n, helpful_reviews = #(helpful_vote > 5)                 */
+/*   Ru = helpful / n; user_y = 1 if Ru >= 0.7, 0 if Ru <= 0.3, else -1       */
+/*   user_x [n_users, 7] (USER_FEATURE_KEYS order) = Ru, the natural-log      */
+/*     entropy of the histogram of ri (bins 1..5 in order), #(ri in {1, 5}) / */
+/*     n, mean |ri - item_rbar[item]|, (records with a timestamp) - (distinct */
+/*     buckets), (sum over L > 0 of unique / L) / n, mean |L -                */
+/*     global_avg_len|                                                        */
+/* A user with no record gets a NaN row, label -1 and zero counts. A row of   */
+/* at most 512 records is summed by one lane in file order, a longer one by   */
+/* one workgroup in a fixed shape. Size query with workspace == NULL; the     */
+/* workspace holds 16 bytes per record (what the pass reads of a record,      */
+/* packed by a streaming launch so that the gather by record id touches one   */
+/* memory line per record, not five).                                         */
+typedef struct {
+  const int32_t *u_indptr;    /* [n_users + 1] */
+  const int32_t *u_eid;       /* [n] */
+  const int32_t *b_indptr;    /* [n_users + 2] (row n_users: no timestamp) */
+  const int32_t *b_bucket;    /* [n] sorted within a row */
+  const double *item_rbar;    /* [n_items] (bbgr_feat_items) */
+  double global_avg_len;      /* sum of n_tokens / max(n, 1) */
+  float *user_x;              /* [n_users, 7] */
+  int64_t *user_y;            /* [n_users] */
+  int32_t *total_reviews;     /* [n_users] */
+  int32_t *helpful_reviews;   /* [n_users] */
+} bbgr_feat_user_args;
+int bbgr_feat_users(const bbgr_feat_columns *c, const bbgr_feat_user_args *args,
+                    void *workspace, size_t *workspace_bytes, bbgr_stream_t stream);
+
+/* edge_attr [n, 5] (EDGE_ATTR_KEYS order), in double, rounded at the store:  */
+/*   verified, 1 - |rating - item_x[item, 0]| / 4, rating, (timestamp -       */
+/*   ts_min) / (ts_max - ts_min) (NaN without a timestamp or when ts_max ==   */
+/*   ts_min), helpful_vote. One streaming pass; edge_attr 16-byte aligned.    */
+int bbgr_feat_edges(const bbgr_feat_columns *c, const float *item_x, int64_t ts_min,
+                    int64_t ts_max, float *edge_attr, bbgr_stream_t stream);
+
+/* ------------------------------------------------------------------------- */
 /* Blueprint names (SURVEY §8(b)'s ABI sketch), thin forms of the above.      */
 /* ------------------------------------------------------------------------- */
 /* Y = diag(row_scale) A diag(col_scale) X (either scale NULL = ones), one    */
