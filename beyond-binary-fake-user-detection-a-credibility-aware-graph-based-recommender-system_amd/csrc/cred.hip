@@ -22,6 +22,8 @@
 //                      w1t) from the input-order weights and each edge's dst:
 //                      coalesced, no scatter. (Without dst: the scatter
 //                      through perm in seg_scale_kernel.)
+// Non-finite attributes follow torch: a NaN passes both clamps, so its edge's
+// raw weight and every normalised weight of that destination are NaN.
 #include "common.h"
 
 namespace bbgr {
@@ -49,9 +51,11 @@ __global__ void ewa_raw_kernel(long E, const float *attr, long lda, int cv, int 
   const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= E) return;
   const float *a = attr + e * lda;
-  const float verified = fminf(fmaxf(a[cv], 0.f), 1.f);   // clamp(0, 1)
+  // torch's clamp keeps a NaN; fmaxf / fminf return the other operand
+  const float v = a[cv];
+  const float verified = v != v ? v : fminf(fmaxf(v, 0.f), 1.f);   // clamp(0, 1)
   const float w = beta * verified + gamma * a[ca];
-  out[e] = fmaxf(w, 0.f);                                  // clamp(min=0)
+  out[e] = w != w ? w : fmaxf(w, 0.f);                              // clamp(min=0)
 }
 
 __global__ void raw_csr_kernel(long E, const int *perm, const float *raw, float *out) {

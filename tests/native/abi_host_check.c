@@ -166,6 +166,64 @@ int main(void) {
     r.n_users_listed = -1;
     expect_error("rows_mark negative count", bbgr_rows_mark(&r, NULL));
   }
+  {
+    /* bbgr_ewa_normalize: a planned CSR of 1000 edges (3 chunks, 1 split row) whose
+     * arrays are never read: every call returns before a launch */
+    bbgr_csr e;
+    memset(&e, 0, sizeof e);
+    e.n_rows = 40;
+    e.n_cols = 50;
+    e.nnz = 1000;
+    e.indptr = e.indices = e.chunks = e.split = (const int32_t *)f4;
+    e.long_threshold = 64;
+    e.chunk_edges = 2048;
+    e.n_chunks = 3;
+    e.n_split = 1;
+    const int32_t *i4 = (const int32_t *)f4;
+    size_t need = 0, own = 0, have;
+    expect_error("ewa null csr", bbgr_ewa_normalize(NULL, i4, i4, NULL, f4, 5, 0, 1, 1.f, 1.f,
+                                                    1e-12f, f4, f4, f4, f4, &need, NULL));
+    expect_error("ewa null size", bbgr_ewa_normalize(&e, i4, i4, NULL, f4, 5, 0, 1, 1.f, 1.f,
+                                                     1e-12f, f4, f4, f4, f4, NULL, NULL));
+    expect_ok("ewa query", bbgr_ewa_normalize(&e, NULL, NULL, NULL, NULL, 0, -1, -1, 1.f, 1.f,
+                                              1e-12f, f4, NULL, NULL, NULL, &need, NULL));
+    expect_ok("ewa query own raw", bbgr_ewa_normalize(&e, NULL, NULL, NULL, NULL, 0, -1, -1, 1.f,
+                                                      1.f, 1e-12f, NULL, NULL, NULL, NULL, &own,
+                                                      NULL));
+    if (need != 4096 + 256 + 256 || own != need + 4096) {
+      fprintf(stderr, "FAIL ewa workspace sizes %zu %zu\n", need, own);
+      ++failures;
+    }
+    have = need - 1;
+    if (bbgr_ewa_normalize(&e, i4, i4, NULL, f4, 5, 0, 1, 1.f, 1.f, 1e-12f, f4, f4, f4, f4,
+                           &have, NULL) != BBGR_ERR_WORKSPACE) {
+      fprintf(stderr, "FAIL ewa small workspace: %s\n", bbgr_last_error());
+      ++failures;
+    }
+    have = own;
+    expect_error("ewa null perm", bbgr_ewa_normalize(&e, NULL, i4, NULL, f4, 5, 0, 1, 1.f, 1.f,
+                                                     1e-12f, f4, f4, f4, f4, &have, NULL));
+    expect_error("ewa no weights", bbgr_ewa_normalize(&e, i4, i4, NULL, NULL, 5, 0, 1, 1.f, 1.f,
+                                                      1e-12f, f4, f4, f4, f4, &have, NULL));
+    expect_error("ewa negative column", bbgr_ewa_normalize(&e, i4, i4, NULL, f4, 5, -1, 1, 1.f,
+                                                           1.f, 1e-12f, f4, f4, f4, f4, &have,
+                                                           NULL));
+    expect_error("ewa column past lda", bbgr_ewa_normalize(&e, i4, i4, NULL, f4, 5, 0, 5, 1.f,
+                                                           1.f, 1e-12f, f4, f4, f4, f4, &have,
+                                                           NULL));
+    e.split = NULL;
+    expect_error("ewa null split", bbgr_ewa_normalize(&e, i4, i4, NULL, f4, 5, 0, 1, 1.f, 1.f,
+                                                      1e-12f, f4, f4, f4, f4, &have, NULL));
+    e.chunks = NULL;
+    expect_error("ewa null chunks", bbgr_ewa_normalize(&e, i4, i4, NULL, f4, 5, 0, 1, 1.f, 1.f,
+                                                       1e-12f, f4, f4, f4, f4, &have, NULL));
+    e.indptr = NULL;
+    expect_error("ewa null indptr", bbgr_ewa_normalize(&e, i4, i4, NULL, f4, 5, 0, 1, 1.f, 1.f,
+                                                       1e-12f, f4, f4, f4, f4, &have, NULL));
+    e.nnz = 0;   /* nothing to do: no pointer is needed */
+    expect_ok("ewa empty", bbgr_ewa_normalize(&e, NULL, NULL, NULL, NULL, 0, -1, -1, 1.f, 1.f,
+                                              1e-12f, NULL, NULL, NULL, f4, &have, NULL));
+  }
   expect_error("eval sampled null", bbgr_eval_sampled(NULL, NULL, NULL, NULL));
   expect_error("eval full null", bbgr_eval_full(NULL, NULL, NULL, NULL));
 
