@@ -5,7 +5,8 @@ every quantity is a plain Python loop or sum over such a list, in Python float
 (double), rounded to float32 only at the very end, where the reference's
 ``np.asarray(.., float32)`` rounds. Sums run in file order, the order in which
 the reference's per-record loops add. The reference for
-tests/test_features_host.py and tests/test_gpu_features.py.
+tests/test_features_host.py, tests/test_gpu_features.py and
+tests/test_gpu_features_edges.py.
 A helper, not a test module."""
 import math
 
@@ -33,6 +34,28 @@ def _filed(keys):
     for e, k in enumerate(keys):
         out.setdefault(k, []).append(e)
     return out
+
+
+def user_sum_terms(cols) -> dict:
+    """Per record, the double terms whose per-user sums features_ref divides
+    into user columns 3, 5 and 6, formed exactly as features_ref forms them
+    (a record without words adds nothing to column 5: its term is 0.0), as
+    float64 arrays. For an order-free mean (math.fsum) over a user's records:
+    tests/test_gpu_features_edges.py."""
+    item = np.asarray(cols.item).tolist()
+    rating = np.asarray(cols.rating, np.float32).astype(np.float64).tolist()
+    words = np.asarray(cols.n_tokens).tolist()
+    distinct = np.asarray(cols.n_unique_tokens).tolist()
+    n_rec = len(item)
+    stars = [star(r) for r in rating]
+    mean_star = {i: sum(stars[e] for e in recs) / len(recs) for i, recs in _filed(item).items()}
+    avg_words = sum(words) / max(n_rec, 1)
+    return {
+        3: np.asarray([abs(stars[e] - mean_star[item[e]]) for e in range(n_rec)], np.float64),
+        5: np.asarray([distinct[e] / words[e] if words[e] > 0 else 0.0 for e in range(n_rec)],
+                      np.float64),
+        6: np.asarray([abs(words[e] - avg_words) for e in range(n_rec)], np.float64),
+    }
 
 
 def features_ref(cols, num_users: int, num_items: int) -> dict:
