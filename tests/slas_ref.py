@@ -4,6 +4,8 @@ profiles through torch as the reference forms them. Every sampling call can be
 replaced by supplied picks (``pick(kind, row, nbrs, eids, k)`` returns the
 chosen positions in the eligible arrays, in output order); without it the
 draws are ``rng.choice(n, k, replace=False, p=w)`` on ``default_rng(42)``.
+Below it, the sampler's own keys restated (Philox4x32-10, u24, float64 keys)
+and ``check_picks``, the tolerant form of "the k smallest keys, ascending".
 A helper, not a test module."""
 import numpy as np
 import torch
@@ -160,3 +162,121 @@ def picks_from_device(last_picks, seed_users):
         where = {int(x): p for p, x in enumerate(eids.tolist())}
         return [where[int(x)] for x in e[j, :k]]
     return pick
+
+
+# -- the sampler's keys, restated on the host -------------------------------------
+# bbgr.h: slot j of a row with more than k eligible slots gets the key
+# -log(U_j) / w_j, U_j from the first Philox4x32-10 word at counter
+# {counter, stage, row id, slot position in the full row}, key = seed.
+_M32 = np.uint64(0xFFFFFFFF)
+_PHILOX_M0, _PHILOX_M1 = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57)
+_PHILOX_W0, _PHILOX_W1 = 0x9E3779B9, 0xBB67AE85
+FLT_MIN, FLT_MAX = 1.17549435e-38, 3.40282347e38
+
+
+def philox4x32_10(c0, c1, c2, c3, k0, k1):
+    """Philox4x32-10 as csrc/common.h states it, vectorised: uint64 arithmetic
+    masked to 32 bits. Returns the four output words (uint64 arrays < 2^32)."""
+    c0, c1, c2, c3 = np.broadcast_arrays(*(np.asarray(c, np.uint64) & _M32
+                                           for c in (c0, c1, c2, c3)))
+    k0, k1 = int(k0) & 0xFFFFFFFF, int(k1) & 0xFFFFFFFF
+    for _ in range(10):
+        p0 = _PHILOX_M0 * c0                      # 32 x 32 bits: no overflow in 64
+        p1 = _PHILOX_M1 * c2
+        c0, c1, c2, c3 = ((p1 >> np.uint64(32)) ^ c1 ^ np.uint64(k0), p1 & _M32,
+                          (p0 >> np.uint64(32)) ^ c3 ^ np.uint64(k1), p0 & _M32)
+        k0, k1 = (k0 + _PHILOX_W0) & 0xFFFFFFFF, (k1 + _PHILOX_W1) & 0xFFFFFFFF
+    return c0, c1, c2, c3
+
+
+def slas_u24(seed, counter, stage, row, positions):
+    """The integer (x0 >> 8) + 1 in [1, 2^24] behind U = u24 * 2^-24.
+    `positions` are slot positions in the full row (e - indptr[row]), not ranks
+    among the eligible slots; `row` may be an array of the same shape."""
+    seed = int(seed)
+    x0 = philox4x32_10(counter, stage, row, positions, seed & 0xFFFFFFFF, seed >> 32)[0]
+    return (x0 >> np.uint64(8)).astype(np.int64) + 1
+
+
+def slas_weights64(dot64, kappa, labels=None, upweight=0.0):
+    """clip(exp(kappa * dot) * (1 + upweight where label >= 0), FLT_MIN, FLT_MAX)
+    in float64; a NaN weight becomes FLT_MIN as fminf(fmaxf(.)) makes it."""
+    with np.errstate(over="ignore", invalid="ignore"):
+        w = np.exp(float(kappa) * np.asarray(dot64, np.float64))
+        if labels is not None:
+            w = w * np.where(np.asarray(labels) >= 0, 1.0 + float(upweight), 1.0)
+    return np.clip(np.where(np.isnan(w), FLT_MIN, w), FLT_MIN, FLT_MAX)
+
+
+def slas_keys64(u24, w, eligible=None):
+    """float64 keys -log(u24 * 2^-24) / w, +inf at the ineligible slots."""
+    keys = -np.log(np.asarray(u24, np.float64) * 2.0 ** -24) / np.asarray(w, np.float64)
+    keys = np.abs(keys)                              # -log(1) / w is -0.0
+    return keys if eligible is None else np.where(eligible, keys, np.inf)
+
+
+def slot_rows(ptr):
+    """(row id, position in the row) of every slot of a CSR."""
+    ptr = np.asarray(ptr, np.int64)
+    row = np.repeat(np.arange(ptr.size - 1, dtype=np.int64), np.diff(ptr))
+    return row, np.arange(ptr[-1], dtype=np.int64) - ptr[row]
+
+
+# The relative error of a device key against slas_keys64, and check_picks' delta.
+#   exponent: the fmaf chain of the dot product rounds F times and kappa * dot
+#     once, each by at most 2^-24 of a value of magnitude <= 1 (unit profiles,
+#     Cauchy-Schwarz for the partial sums) resp. <= |kappa|: an absolute error
+#     of at most (F + 1) * 2^-24 * |kappa| in the exponent, the same relative
+#     error in w (first order);
+#   expf and logf: 3 ulp each; the division: 2.5 ulp; the label multiply: 0.5 ulp
+#     (correctly rounded). One ulp is at most 2^-23 relative. These are the
+#     OpenCL 3.0 full-profile bounds (table "ULP values for single precision
+#     built-in math functions": exp <= 3, log <= 3, x / y <= 2.5), which the
+#     ROCm device library's expf / logf / division are specified against. HIP's
+#     math API page lists measured maxima per function, none above these, so
+#     the OpenCL figures are the looser, safe choice.
+# Two keys are compared and a factor two covers slack: delta = 4 * budget.
+_KEY_ULPS = 3.0 + 3.0 + 2.5 + 0.5
+
+
+def key_error_budget(F, kappa):
+    return (F + 1) * 2.0 ** -24 * abs(float(kappa)) + _KEY_ULPS * 2.0 ** -23
+
+
+def pick_delta(F, kappa):
+    return 4.0 * key_error_budget(F, kappa)
+
+
+def check_picks(keys64, eligible, picked, delta, u24=None, w=None):
+    """The tolerant form of "the k smallest keys, ascending, equal keys the
+    lower slot first" for one row: `picked` are slot positions in output order.
+    Where every gap between neighbouring keys exceeds delta this is equality
+    with argsort. Returns the largest relative inversion met (0 if none):
+    1 - later / earlier over consecutive picks and over (last pick, best
+    unpicked slot)."""
+    keys64 = np.asarray(keys64, np.float64)
+    eligible = np.asarray(eligible, bool)
+    p = np.asarray(picked, np.int64)
+    assert p.size >= 1
+    assert ((p >= 0) & (p < keys64.size)).all(), ("position out of the row", p)
+    assert np.unique(p).size == p.size, ("a slot picked twice", p)
+    assert eligible[p].all(), ("an ineligible slot picked", p[~eligible[p]])
+    kp = keys64[p]
+    assert np.isfinite(kp).all(), ("a pick without a finite key", p)
+    lo = kp[:-1] * (1.0 - delta)
+    assert (kp[1:] >= lo).all(), ("picks not in ascending key order",
+                                  p[:-1][kp[1:] < lo], kp[:-1][kp[1:] < lo], kp[1:][kp[1:] < lo])
+    rest = eligible.copy()
+    rest[p] = False
+    best_rest = keys64[rest].min() if rest.any() else np.inf
+    assert best_rest >= kp[-1] * (1.0 - delta), ("an unpicked slot beats the last pick",
+                                                 int(np.flatnonzero(rest)[keys64[rest].argmin()]),
+                                                 best_rest, kp[-1])
+    if u24 is not None:
+        u24, w = np.asarray(u24), np.asarray(w)
+        tie = (u24[p[1:]] == u24[p[:-1]]) & (w[p[1:]] == w[p[:-1]])
+        assert (p[1:][tie] > p[:-1][tie]).all(), ("equal keys, higher slot first", p[:-1][tie])
+    later = np.append(kp[1:], best_rest)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        inv = np.where(kp > 0, 1.0 - later / kp, 0.0)
+    return float(max(inv.max(), 0.0))
