@@ -6,6 +6,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <string>
+#include <type_traits>
 
 #include "bbgr.h"
 
@@ -38,12 +39,28 @@ inline int hip_fail(hipError_t e, const char *what) {
     }                                                                         \
   } while (0)
 
+// BBGR_REQUIRE of a check shared by several entry points: `who` is the entry's
+// name, so the message reads as if the entry had spelled the check out itself.
+#define BBGR_REQUIRE_IN(who, cond, msg)                                       \
+  do {                                                                        \
+    if (!(cond)) {                                                            \
+      ::bbgr::set_error("%s: %s", who, msg);                                  \
+      return BBGR_ERR_INVALID;                                                \
+    }                                                                         \
+  } while (0)
+
 inline hipStream_t as_stream(bbgr_stream_t s) {
   return reinterpret_cast<hipStream_t>(s);
 }
 
 inline bool aligned16(const void *p) {
   return (reinterpret_cast<uintptr_t>(p) & 15u) == 0;
+}
+
+// The table rule of the entry points: a d-wide fp32 table (nullable) is 16-byte
+// aligned with a row stride ld >= d, ld % 4 == 0.
+inline bool ld_ok(const void *p, long ld, int d) {
+  return p == nullptr || (aligned16(p) && ld >= d && (ld & 3) == 0);
 }
 
 // Round a workspace carve offset up to 256 bytes.
@@ -92,6 +109,36 @@ template <int D> struct RowShape {
 
 inline bool supported_width(int d) {
   return d == 8 || d == 16 || d == 32 || d == 64 || d == 128 || d == 256;
+}
+
+// The refusal of any other width (`wide`: of an entry that takes 64, 128, 256).
+inline int unsupported_width(const char *who, int d, bool wide = false) {
+  set_error("%s: embedding dim %d unsupported (%s)", who, d,
+            wide ? "64, 128, 256" : "8, 16, 32, 64, 128, 256");
+  return BBGR_ERR_UNSUPPORTED;
+}
+
+// Runtime width -> template argument: calls f(std::integral_constant<int, D>{})
+// for the supported width d (every other was refused before) and returns what
+// f returns; inside f, `decltype(W)::value` is the compile-time D.
+template <typename F> inline auto for_width(int d, F &&f) {
+  switch (d) {
+    case 8: return f(std::integral_constant<int, 8>{});
+    case 16: return f(std::integral_constant<int, 16>{});
+    case 32: return f(std::integral_constant<int, 32>{});
+    case 64: return f(std::integral_constant<int, 64>{});
+    case 128: return f(std::integral_constant<int, 128>{});
+    default: return f(std::integral_constant<int, 256>{});
+  }
+}
+
+// The same for the entries that take 64, 128 or 256 only.
+template <typename F> inline auto for_wide_width(int d, F &&f) {
+  switch (d) {
+    case 64: return f(std::integral_constant<int, 64>{});
+    case 128: return f(std::integral_constant<int, 128>{});
+    default: return f(std::integral_constant<int, 256>{});
+  }
 }
 
 // Streaming (non-temporal) 16-byte loads / stores: data touched once per

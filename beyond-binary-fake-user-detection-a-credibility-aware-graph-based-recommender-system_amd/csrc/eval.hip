@@ -892,10 +892,7 @@ extern "C" int bbgr_eval_sampled(const bbgr_eval_args *a, void *workspace,
     return BBGR_ERR_WORKSPACE;
   }
   const int d = a->d;
-  if (d != 64 && d != 128 && d != 256) {
-    set_error("bbgr_eval_sampled: embedding dim %d unsupported (64, 128, 256)", d);
-    return BBGR_ERR_UNSUPPORTED;
-  }
+  if (d != 64 && d != 128 && d != 256) return unsupported_width("bbgr_eval_sampled", d, true);
   hipStream_t st = as_stream(stream);
   if (a->n_users > 0) {
     BBGR_REQUIRE(a->pos_rank, "bbgr_eval_sampled: null pos_rank");
@@ -923,20 +920,11 @@ extern "C" int bbgr_eval_sampled(const bbgr_eval_args *a, void *workspace,
     BBGR_HIP(hipMemsetAsync(a->topk, 0xff, sizeof(int) * (size_t)a->n_users * a->k_max, st));
     const unsigned grid = (unsigned)((a->n_users + 15) / 16);
     const bool small = 1 + a->n_neg <= 128;
-    switch (d) {
-      case 64:
-        if (small) hipLaunchKernelGGL((eval_sampled_kernel<64, 128>), dim3(grid), dim3(256), 0, st, P);
-        else hipLaunchKernelGGL((eval_sampled_kernel<64, 256>), dim3(grid), dim3(256), 0, st, P);
-        break;
-      case 128:
-        if (small) hipLaunchKernelGGL((eval_sampled_kernel<128, 128>), dim3(grid), dim3(256), 0, st, P);
-        else hipLaunchKernelGGL((eval_sampled_kernel<128, 256>), dim3(grid), dim3(256), 0, st, P);
-        break;
-      default:
-        if (small) hipLaunchKernelGGL((eval_sampled_kernel<256, 128>), dim3(grid), dim3(256), 0, st, P);
-        else hipLaunchKernelGGL((eval_sampled_kernel<256, 256>), dim3(grid), dim3(256), 0, st, P);
-        break;
-    }
+    for_wide_width(d, [&](auto W) {
+      constexpr int D = decltype(W)::value;
+      void (*k)(EvalParams) = small ? eval_sampled_kernel<D, 128> : eval_sampled_kernel<D, 256>;
+      hipLaunchKernelGGL(k, dim3(grid), dim3(256), 0, st, P);
+    });
     BBGR_LAUNCHED("eval_sampled_kernel");
   }
   return launch_terms(a, false, L, static_cast<char *>(workspace), st);

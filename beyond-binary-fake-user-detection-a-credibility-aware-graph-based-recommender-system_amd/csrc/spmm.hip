@@ -1350,28 +1350,28 @@ __global__ __launch_bounds__(256) void spmm_bf16_masked_pair_kernel(SpmmParams P
   spmm_body<D, WMODE, true, true, false, TAG_NONE, true>(P);
 }
 
+using SpmmKernel = void (*)(SpmmParams);
+
+// Workgroups of a launch: one per long-row chunk, then the short rows, one per
+// 16-lane group (two on a two-row CSR, 16 / LANES where rows are narrow).
+template <int D>
+static long spmm_grid(const SpmmParams &P) {
+  const long short_rows = P.row_list ? P.n_row_list : (long)(P.row_end - P.row_begin);
+  const long per_block = D < 64 ? 16 * (16 / (D / 4)) : (P.pair_rows ? 32 : 16);
+  return (long)P.n_chunks + (short_rows + per_block - 1) / per_block;
+}
+
 template <int D, int WMODE>
 static int launch_spmm_bf16(const SpmmParams &P, hipStream_t st) {
   const bool masked = P.row_mask || P.row_list;
-  const long short_rows = P.row_list ? P.n_row_list : (long)(P.row_end - P.row_begin);
-  const long short_blocks = P.pair_rows ? (short_rows + 31) / 32 : (short_rows + 15) / 16;
-  const long grid = (long)P.n_chunks + short_blocks;
+  const SpmmKernel k =
+      P.pair_rows ? (masked ? spmm_bf16_masked_pair_kernel<D, WMODE> : spmm_bf16_pair_kernel<D, WMODE>)
+                  : (masked ? spmm_bf16_masked_kernel<D, WMODE> : spmm_bf16_kernel<D, WMODE>);
+  const long grid = spmm_grid<D>(P);
   if (grid <= 0) return BBGR_OK;
-  const dim3 gd((unsigned)grid), bd(256);
-  if (P.pair_rows) {
-    if (masked) hipLaunchKernelGGL((spmm_bf16_masked_pair_kernel<D, WMODE>), gd, bd, 0, st, P);
-    else hipLaunchKernelGGL((spmm_bf16_pair_kernel<D, WMODE>), gd, bd, 0, st, P);
-  } else {
-    if (masked) hipLaunchKernelGGL((spmm_bf16_masked_kernel<D, WMODE>), gd, bd, 0, st, P);
-    else hipLaunchKernelGGL((spmm_bf16_kernel<D, WMODE>), gd, bd, 0, st, P);
-  }
+  hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(256), 0, st, P);
   BBGR_LAUNCHED("spmm_bf16_kernel");
   return BBGR_OK;
-}
-
-template <int D>
-static int dispatch_bf16(const SpmmParams &P, int wmode, hipStream_t st) {
-  return wmode == 1 ? launch_spmm_bf16<D, 1>(P, st) : launch_spmm_bf16<D, 0>(P, st);
 }
 
 // fp32 table -> bf16 table, 4 columns per thread (16-byte load, 8-byte store)
@@ -1407,54 +1407,47 @@ __global__ __launch_bounds__(256) void epilogue_kernel(SpmmParams P, const float
   epilogue<D>(P, (int)row, lane, T);
 }
 
+// The fp32 kernel of a launch. Wide rows (d >= 64): a two-row CSR takes the
+// pair forms, tagged before masked before fused Adam; else a slot bitmap takes
+// its own kernel. Everything left (narrow rows too) is one row per group:
+// masked, fused Adam or plain. `tag_read`: the indices are the tagged copy.
 template <int D, int WMODE>
-static int launch_spmm(const SpmmParams &P, int n_split, hipStream_t st, bool tag_read) {
+static SpmmKernel pick_spmm(const SpmmParams &P, bool tag_read) {
   const bool masked = P.src_mask || P.row_mask || P.row_list || tag_read;
-  const long short_rows = P.row_list ? P.n_row_list : (long)(P.row_end - P.row_begin);
-  const bool pair = D >= 64 && P.pair_rows;
-  const long per_block = D < 64 ? 16 * (16 / (D / 4)) : (pair ? 32 : 16);
-  const long short_blocks = (short_rows + per_block - 1) / per_block;
-  const long grid = (long)P.n_chunks + short_blocks;
-  if ((P.tag_out || tag_read) && !(D >= 64 && pair)) {
+  if constexpr (D >= 64) {
+    if (P.pair_rows)
+      return tag_read   ? spmm_masked_pair_tagged_kernel<D, WMODE>
+             : P.tag_out ? spmm_pair_tag_kernel<D, WMODE>
+             : masked    ? spmm_masked_pair_kernel<D, WMODE>
+             : P.adam_p  ? spmm_adam_pair_kernel<D, WMODE>
+                         : spmm_pair_kernel<D, WMODE>;
+    if (P.src_bits) return spmm_bits_kernel<D, WMODE>;
+  }
+  return masked     ? spmm_masked_kernel<D, WMODE>
+         : P.adam_p ? spmm_adam_kernel<D, WMODE>
+                    : spmm_kernel<D, WMODE>;
+}
+
+template <int D, int WMODE>
+static int launch_spmm(const SpmmParams &P, hipStream_t st, bool tag_read) {
+  if ((P.tag_out || tag_read) && !P.pair_rows) {   // pair_rows: a two-row CSR at d >= 64
     set_error("bbgr_spmm: tagged indices need a two-row CSR (average degree <= 24) and d >= 64");
     return BBGR_ERR_UNSUPPORTED;
   }
-  if (grid > 0) {
-    const dim3 gd((unsigned)grid), bd(256);
-    if constexpr (D >= 64) {
-      if (pair) {
-        if (tag_read) hipLaunchKernelGGL((spmm_masked_pair_tagged_kernel<D, WMODE>), gd, bd, 0, st, P);
-        else if (P.tag_out) hipLaunchKernelGGL((spmm_pair_tag_kernel<D, WMODE>), gd, bd, 0, st, P);
-        else if (masked) hipLaunchKernelGGL((spmm_masked_pair_kernel<D, WMODE>), gd, bd, 0, st, P);
-        else if (P.adam_p) hipLaunchKernelGGL((spmm_adam_pair_kernel<D, WMODE>), gd, bd, 0, st, P);
-        else hipLaunchKernelGGL((spmm_pair_kernel<D, WMODE>), gd, bd, 0, st, P);
-        BBGR_LAUNCHED("spmm_kernel");
-        return BBGR_OK;
-      }
-    }
-    if constexpr (D >= 64) {
-      if (P.src_bits) {
-        hipLaunchKernelGGL((spmm_bits_kernel<D, WMODE>), gd, bd, 0, st, P);
-        BBGR_LAUNCHED("spmm_kernel");
-        return BBGR_OK;
-      }
-    }
-    if (masked) hipLaunchKernelGGL((spmm_masked_kernel<D, WMODE>), gd, bd, 0, st, P);
-    else if (P.adam_p) hipLaunchKernelGGL((spmm_adam_kernel<D, WMODE>), gd, bd, 0, st, P);
-    else hipLaunchKernelGGL((spmm_kernel<D, WMODE>), gd, bd, 0, st, P);
-    BBGR_LAUNCHED("spmm_kernel");
-  }
-  (void)n_split;   // split rows are finished in-launch (split_row_arrive)
+  const SpmmKernel k = pick_spmm<D, WMODE>(P, tag_read);
+  const long grid = spmm_grid<D>(P);
+  if (grid <= 0) return BBGR_OK;
+  hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(256), 0, st, P);
+  BBGR_LAUNCHED("spmm_kernel");
   return BBGR_OK;
 }
 
 template <int D>
-static int dispatch_wmode(const SpmmParams &P, int wmode, int n_split,
-                          hipStream_t st, bool tag_read) {
+static int dispatch_wmode(const SpmmParams &P, int wmode, hipStream_t st, bool tag_read) {
   switch (wmode) {
-    case 0: return launch_spmm<D, 0>(P, n_split, st, tag_read);
-    case 1: return launch_spmm<D, 1>(P, n_split, st, tag_read);
-    case 2: return launch_spmm<D, 2>(P, n_split, st, tag_read);
+    case 0: return launch_spmm<D, 0>(P, st, tag_read);
+    case 1: return launch_spmm<D, 1>(P, st, tag_read);
+    case 2: return launch_spmm<D, 2>(P, st, tag_read);
   }
   set_error("bbgr_spmm: weight_mode %d not in {0,1,2}", wmode);
   return BBGR_ERR_INVALID;
@@ -1467,10 +1460,6 @@ static int pair_rows(const bbgr_csr *csr) {
   const char *env = getenv("BBGR_SPMM_PAIR");
   if (env && *env) return atoi(env) != 0;
   return csr->n_rows > 0 && csr->nnz <= 24L * csr->n_rows;
-}
-
-static bool ld_ok(const float *p, long ld, int d) {
-  return p == nullptr || (aligned16(p) && ld >= d && (ld & 3) == 0);
 }
 
 }  // namespace bbgr
@@ -1538,10 +1527,7 @@ extern "C" int bbgr_epilogue(int32_t n_rows, const float *t, int64_t ldt,
                              const bbgr_spmm_args *a, bbgr_stream_t stream) {
   BBGR_REQUIRE(a && n_rows >= 0, "bbgr_epilogue: bad args");
   const int d = a->d;
-  if (!supported_width(d)) {
-    set_error("bbgr_epilogue: embedding dim %d unsupported (8, 16, 32, 64, 128, 256)", d);
-    return BBGR_ERR_UNSUPPORTED;
-  }
+  if (!supported_width(d)) return unsupported_width("bbgr_epilogue", d);
   if (n_rows == 0) return BBGR_OK;
   BBGR_REQUIRE(t && ld_ok(t, ldt, d) && ld_ok(a->y, a->ldy, d) && ld_ok(a->add, a->ldadd, d) &&
                    ld_ok(a->acc_in, a->ldacc_in, d) && ld_ok(a->acc_out, a->ldacc_out, d) &&
@@ -1558,31 +1544,95 @@ extern "C" int bbgr_epilogue(int32_t n_rows, const float *t, int64_t ldt,
   const long n_in = a->row_list ? (long)a->n_row_list : (long)n_rows;
   if (n_in == 0) return BBGR_OK;
   const unsigned grid = (unsigned)((n_in + 15) / 16);
-  hipStream_t st = as_stream(stream);
-  switch (d) {
-    case 8: hipLaunchKernelGGL(epilogue_kernel<8>, dim3(grid), dim3(256), 0, st, P, t, (long)ldt); break;
-    case 16: hipLaunchKernelGGL(epilogue_kernel<16>, dim3(grid), dim3(256), 0, st, P, t, (long)ldt); break;
-    case 32: hipLaunchKernelGGL(epilogue_kernel<32>, dim3(grid), dim3(256), 0, st, P, t, (long)ldt); break;
-    case 64: hipLaunchKernelGGL(epilogue_kernel<64>, dim3(grid), dim3(256), 0, st, P, t, (long)ldt); break;
-    case 128: hipLaunchKernelGGL(epilogue_kernel<128>, dim3(grid), dim3(256), 0, st, P, t, (long)ldt); break;
-    default: hipLaunchKernelGGL(epilogue_kernel<256>, dim3(grid), dim3(256), 0, st, P, t, (long)ldt); break;
-  }
+  for_width(d, [&](auto W) {
+    hipLaunchKernelGGL(epilogue_kernel<decltype(W)::value>, dim3(grid), dim3(256), 0,
+                       as_stream(stream), P, t, (long)ldt);
+  });
   BBGR_LAUNCHED("epilogue_kernel");
   return BBGR_OK;
+}
+
+// The checks and the SpmmParams fields that bbgr_spmm and bbgr_spmm_bf16 share
+// (`who`: the entry's name in the message). Each entry runs check_csr, its own
+// width / table / feature checks, then check_rows: the order of its refusals.
+static int check_csr(const char *who, const bbgr_csr *csr) {
+  BBGR_REQUIRE_IN(who, csr->n_rows >= 0 && csr->n_cols >= 0 && csr->nnz >= 0, "negative csr size");
+  BBGR_REQUIRE_IN(who, csr->indptr && (csr->nnz == 0 || csr->indices), "null csr arrays");
+  return BBGR_OK;
+}
+
+// The load-balance plan, the row list and the range of a launch
+static int check_rows(const char *who, const bbgr_csr *csr, const bbgr_spmm_args *a) {
+  BBGR_REQUIRE_IN(who, csr->n_chunks == 0 || csr->chunks, "plan chunks missing");
+  BBGR_REQUIRE_IN(who, csr->n_split == 0 || (csr->split && a->partial),
+                  "split rows need plan + partial workspace");
+  BBGR_REQUIRE_IN(who, csr->n_chunks == 0 || csr->long_threshold > 0,
+                  "plan without long_threshold");
+  BBGR_REQUIRE_IN(who, !a->row_count || a->row_list, "row_count needs row_list");
+  if (a->use_range) {
+    const int *r = a->range;
+    BBGR_REQUIRE_IN(who,
+                    r[0] >= 0 && r[0] <= r[1] && r[1] <= csr->n_rows && r[2] >= 0 &&
+                        r[2] <= r[3] && r[3] <= csr->n_chunks && r[4] >= 0 && r[4] <= r[5] &&
+                        r[5] <= csr->n_split,
+                    "range out of bounds");
+    BBGR_REQUIRE_IN(who, !a->row_list || a->row_mask,
+                    "range with row_list needs row_mask (chunk rows)");
+  }
+  BBGR_REQUIRE_IN(who, !a->row_list || a->n_row_list >= 0, "negative n_row_list");
+  // chunk workgroups of a list launch compute only rows flagged in row_mask:
+  // without the mask, long listed rows would be skipped
+  BBGR_REQUIRE_IN(who, !a->row_list || a->row_mask || csr->n_chunks == 0,
+                  "row_list needs row_mask when the plan has long-row chunks");
+  return BBGR_OK;
+}
+
+// The CSR, plan, row-selection and streaming fields of a checked launch: all
+// but the x / y tables and the epilogue's (fill_epilogue).
+static void fill_launch(SpmmParams &P, const bbgr_csr *csr, const bbgr_spmm_args *a) {
+  P.n_rows = csr->n_rows;
+  P.long_threshold = csr->n_chunks ? csr->long_threshold : 0x7fffffff;
+  P.n_chunks = csr->n_chunks;
+  P.indptr = csr->indptr;
+  P.indices = csr->indices;
+  P.chunks = reinterpret_cast<const int4 *>(csr->chunks);
+  P.split = reinterpret_cast<const int4 *>(csr->split);
+  P.edge_val = a->edge_val;
+  P.col_scale = a->col_scale;
+  P.col_scale_s = a->col_scale_s;
+  P.partial = a->partial;
+  P.chunk_edges = csr->chunk_edges > 0 ? csr->chunk_edges : 2048;
+  P.arrivals = a->partial ? reinterpret_cast<int *>(a->partial + (long)csr->n_chunks * a->d)
+                          : nullptr;
+  P.src_mask = a->src_mask;
+  P.row_mask = a->row_mask;
+  P.row_list = (const long *)a->row_list;
+  P.n_row_list = a->n_row_list;
+  P.row_count = (const long *)a->row_count;
+  P.row_begin = 0;
+  P.row_end = csr->n_rows;
+  P.chunk_begin = 0;
+  if (a->use_range) {
+    const int *r = a->range;
+    if (!a->row_list) {   // with a row list the short rows are the list's entries
+      P.row_begin = r[0];
+      P.row_end = r[1];
+    }
+    P.chunk_begin = r[2];
+    P.n_chunks = r[3] - r[2];
+    P.split = reinterpret_cast<const int4 *>(csr->split) + r[4];
+  }
+  P.pair_rows = a->d >= 64 && pair_rows(csr);
+  P.nt_from = a->stream_from > 0 ? a->stream_from : 0x7fffffff;
+  P.nt_out_from = a->stream_out_from > 0 ? a->stream_out_from : 0x7fffffff;
 }
 
 extern "C" int bbgr_spmm(const bbgr_csr *csr, const bbgr_spmm_args *a,
                          bbgr_stream_t stream) {
   BBGR_REQUIRE(csr && a, "bbgr_spmm: null csr/args");
-  BBGR_REQUIRE(csr->n_rows >= 0 && csr->n_cols >= 0 && csr->nnz >= 0,
-               "bbgr_spmm: negative csr size");
-  BBGR_REQUIRE(csr->indptr && (csr->nnz == 0 || csr->indices),
-               "bbgr_spmm: null csr arrays");
+  if (int rc = check_csr("bbgr_spmm", csr)) return rc;
   const int d = a->d;
-  if (!supported_width(d)) {
-    set_error("bbgr_spmm: embedding dim %d unsupported (8, 16, 32, 64, 128, 256)", d);
-    return BBGR_ERR_UNSUPPORTED;
-  }
+  if (!supported_width(d)) return unsupported_width("bbgr_spmm", d);
   BBGR_REQUIRE(a->x || csr->nnz == 0, "bbgr_spmm: null x");
   BBGR_REQUIRE(ld_ok(a->x, a->ldx, d) && ld_ok(a->y, a->ldy, d) &&
                    ld_ok(a->add, a->ldadd, d) && ld_ok(a->acc_in, a->ldacc_in, d) &&
@@ -1598,63 +1648,7 @@ extern "C" int bbgr_spmm(const bbgr_csr *csr, const bbgr_spmm_args *a,
                "bbgr_spmm: src_bits needs src_mask (narrow and two-row kernels read the mask)");
   BBGR_REQUIRE(a->weight_mode != 1 || a->edge_val, "bbgr_spmm: weight_mode 1 needs edge_val");
   BBGR_REQUIRE(a->weight_mode != 2 || a->col_scale, "bbgr_spmm: weight_mode 2 needs col_scale");
-  BBGR_REQUIRE(csr->n_chunks == 0 || csr->chunks, "bbgr_spmm: plan chunks missing");
-  BBGR_REQUIRE(csr->n_split == 0 || (csr->split && a->partial),
-               "bbgr_spmm: split rows need plan + partial workspace");
-  BBGR_REQUIRE(csr->n_chunks == 0 || csr->long_threshold > 0,
-               "bbgr_spmm: plan without long_threshold");
-
-  SpmmParams P = {};
-  P.n_rows = csr->n_rows;
-  P.long_threshold = csr->n_chunks ? csr->long_threshold : 0x7fffffff;
-  P.n_chunks = csr->n_chunks;
-  P.indptr = csr->indptr;
-  P.indices = csr->indices;
-  P.chunks = reinterpret_cast<const int4 *>(csr->chunks);
-  P.split = reinterpret_cast<const int4 *>(csr->split);
-  P.x = a->x;
-  P.ldx = a->ldx;
-  P.edge_val = a->edge_val;
-  P.col_scale = a->col_scale;
-  P.col_scale_s = a->col_scale_s;
-  fill_epilogue(P, a);
-  P.partial = a->partial;
-  P.chunk_edges = csr->chunk_edges > 0 ? csr->chunk_edges : 2048;
-  P.arrivals = a->partial ? reinterpret_cast<int *>(a->partial + (long)csr->n_chunks * d)
-                          : nullptr;
-  P.src_mask = a->src_mask;
-  P.row_mask = a->row_mask;
-  P.row_list = (const long *)a->row_list;
-  P.n_row_list = a->n_row_list;
-  P.row_count = (const long *)a->row_count;
-  BBGR_REQUIRE(!a->row_count || a->row_list, "bbgr_spmm: row_count needs row_list");
-  int n_split = csr->n_split;
-  P.row_begin = 0;
-  P.row_end = csr->n_rows;
-  P.chunk_begin = 0;
-  if (a->use_range) {
-    const int *r = a->range;
-    BBGR_REQUIRE(r[0] >= 0 && r[0] <= r[1] && r[1] <= csr->n_rows && r[2] >= 0 &&
-                     r[2] <= r[3] && r[3] <= csr->n_chunks && r[4] >= 0 && r[4] <= r[5] &&
-                     r[5] <= csr->n_split,
-                 "bbgr_spmm: range out of bounds");
-    BBGR_REQUIRE(!a->row_list || a->row_mask,
-                 "bbgr_spmm: range with row_list needs row_mask (chunk rows)");
-    if (!a->row_list) {   // with a row list the short rows are the list's entries
-      P.row_begin = r[0];
-      P.row_end = r[1];
-    }
-    P.chunk_begin = r[2];
-    P.n_chunks = r[3] - r[2];
-    P.split = reinterpret_cast<const int4 *>(csr->split) + r[4];
-    n_split = r[5] - r[4];
-  }
-  BBGR_REQUIRE(!a->row_list || a->n_row_list >= 0, "bbgr_spmm: negative n_row_list");
-  // chunk workgroups of a list launch compute only rows flagged in row_mask:
-  // without the mask, long listed rows would be skipped
-  BBGR_REQUIRE(!a->row_list || a->row_mask || csr->n_chunks == 0,
-               "bbgr_spmm: row_list needs row_mask when the plan has long-row chunks");
-  P.pair_rows = d >= 64 && pair_rows(csr);
+  if (int rc = check_rows("bbgr_spmm", csr, a)) return rc;
   // tagged indices: a full launch writes the copy, a masked one reads it
   BBGR_REQUIRE(!a->tag_out || (a->tag_mask && !a->src_tagged && !a->src_mask && !a->row_mask &&
                                !a->row_list && !a->use_range && !a->adam_param),
@@ -1662,21 +1656,19 @@ extern "C" int bbgr_spmm(const bbgr_csr *csr, const bbgr_spmm_args *a,
                "fused Adam)");
   BBGR_REQUIRE(!a->src_tagged || (!a->src_mask && !a->src_bits && !a->adam_param),
                "bbgr_spmm: src_tagged replaces src_mask (no src_mask / src_bits / fused Adam)");
+
+  SpmmParams P = {};
+  fill_launch(P, csr, a);
+  fill_epilogue(P, a);
+  P.x = a->x;
+  P.ldx = a->ldx;
   const bool tag_read = a->src_tagged != nullptr;
   P.tag_out = a->tag_out;
   P.tag_mask = a->tag_mask;
   if (tag_read) P.indices = a->src_tagged;
-  P.nt_from = a->stream_from > 0 ? a->stream_from : 0x7fffffff;
-  P.nt_out_from = a->stream_out_from > 0 ? a->stream_out_from : 0x7fffffff;
-  hipStream_t st = as_stream(stream);
-  switch (d) {
-    case 8: return dispatch_wmode<8>(P, a->weight_mode, n_split, st, tag_read);
-    case 16: return dispatch_wmode<16>(P, a->weight_mode, n_split, st, tag_read);
-    case 32: return dispatch_wmode<32>(P, a->weight_mode, n_split, st, tag_read);
-    case 64: return dispatch_wmode<64>(P, a->weight_mode, n_split, st, tag_read);
-    case 128: return dispatch_wmode<128>(P, a->weight_mode, n_split, st, tag_read);
-    default: return dispatch_wmode<256>(P, a->weight_mode, n_split, st, tag_read);
-  }
+  return for_width(d, [&](auto W) {
+    return dispatch_wmode<decltype(W)::value>(P, a->weight_mode, as_stream(stream), tag_read);
+  });
 }
 
 extern "C" int bbgr_to_bf16(int64_t n_rows, int32_t d, const float *src, int64_t ldsrc,
@@ -1707,15 +1699,9 @@ extern "C" int bbgr_to_bf16(int64_t n_rows, int32_t d, const float *src, int64_t
 extern "C" int bbgr_spmm_bf16(const bbgr_csr *csr, const bbgr_spmm_args *a,
                               const bbgr_spmm_bf16_io *h, bbgr_stream_t stream) {
   BBGR_REQUIRE(csr && a && h, "bbgr_spmm_bf16: null csr/args/io");
-  BBGR_REQUIRE(csr->n_rows >= 0 && csr->n_cols >= 0 && csr->nnz >= 0,
-               "bbgr_spmm_bf16: negative csr size");
-  BBGR_REQUIRE(csr->indptr && (csr->nnz == 0 || csr->indices),
-               "bbgr_spmm_bf16: null csr arrays");
+  if (int rc = check_csr("bbgr_spmm_bf16", csr)) return rc;
   const int d = a->d;
-  if (d != 64 && d != 128 && d != 256) {
-    set_error("bbgr_spmm_bf16: embedding dim %d unsupported (64, 128, 256)", d);
-    return BBGR_ERR_UNSUPPORTED;
-  }
+  if (d != 64 && d != 128 && d != 256) return unsupported_width("bbgr_spmm_bf16", d, true);
   BBGR_REQUIRE(!a->x && !a->y, "bbgr_spmm_bf16: args x / y must be NULL (the io struct replaces them)");
   // the subset forward_steps issues; everything else is bbgr_spmm's
   BBGR_BF16_UNSUPPORTED(a->weight_mode == 2, "bbgr_spmm_bf16: weight_mode 2 unsupported (0 or 1)");
@@ -1742,60 +1728,23 @@ extern "C" int bbgr_spmm_bf16(const bbgr_csr *csr, const bbgr_spmm_args *a,
   BBGR_REQUIRE(ld_ok(a->acc_in, a->ldacc_in, d) && ld_ok(a->acc_out, a->ldacc_out, d),
                "bbgr_spmm_bf16: acc tables must be 16-byte aligned with ld >= d, ld % 4 == 0");
   BBGR_REQUIRE(a->weight_mode != 1 || a->edge_val, "bbgr_spmm_bf16: weight_mode 1 needs edge_val");
-  BBGR_REQUIRE(csr->n_chunks == 0 || csr->chunks, "bbgr_spmm_bf16: plan chunks missing");
-  BBGR_REQUIRE(csr->n_split == 0 || (csr->split && a->partial),
-               "bbgr_spmm_bf16: split rows need plan + partial workspace");
-  BBGR_REQUIRE(csr->n_chunks == 0 || csr->long_threshold > 0,
-               "bbgr_spmm_bf16: plan without long_threshold");
-  BBGR_REQUIRE(!a->row_count || a->row_list, "bbgr_spmm_bf16: row_count needs row_list");
-  BBGR_REQUIRE(!a->row_list || a->n_row_list >= 0, "bbgr_spmm_bf16: negative n_row_list");
-  BBGR_REQUIRE(!a->row_list || a->row_mask || csr->n_chunks == 0,
-               "bbgr_spmm_bf16: row_list needs row_mask when the plan has long-row chunks");
+  if (int rc = check_rows("bbgr_spmm_bf16", csr, a)) return rc;
 
   SpmmParams P = {};
-  P.n_rows = csr->n_rows;
-  P.long_threshold = csr->n_chunks ? csr->long_threshold : 0x7fffffff;
-  P.n_chunks = csr->n_chunks;
-  P.indptr = csr->indptr;
-  P.indices = csr->indices;
-  P.chunks = reinterpret_cast<const int4 *>(csr->chunks);
-  P.split = reinterpret_cast<const int4 *>(csr->split);
+  fill_launch(P, csr, a);
+  // every epilogue field refused above is NULL, and the bf16 bodies read
+  // neither the add table's nor the fused Adam's scalars
+  fill_epilogue(P, a);
   // the 2-byte tables' addresses ride in the fp32 fields (RowVec / src_row)
   P.x = reinterpret_cast<const float *>(h->x);
   P.ldx = h->ldx;
   P.y = reinterpret_cast<float *>(h->y);
   P.ldy = h->ldy;
-  P.edge_val = a->edge_val;
-  P.y_scale = a->y_scale;
-  P.y_scale_s = a->y_scale_s;
-  P.acc_in = a->acc_in;
-  P.ldacc_in = a->ldacc_in;
-  P.acc_out = a->acc_out;
-  P.ldacc_out = a->ldacc_out;
-  P.acc_scale = a->acc_scale;
-  P.acc_scale_s = a->acc_scale_s;
-  P.gamma = a->gamma;
-  P.acc_mask = a->acc_mask;
-  P.partial = a->partial;
-  P.chunk_edges = csr->chunk_edges > 0 ? csr->chunk_edges : 2048;
-  P.arrivals = a->partial ? reinterpret_cast<int *>(a->partial + (long)csr->n_chunks * d)
-                          : nullptr;
-  P.row_mask = a->row_mask;
-  P.row_list = (const long *)a->row_list;
-  P.n_row_list = a->n_row_list;
-  P.row_count = (const long *)a->row_count;
-  P.row_begin = 0;
-  P.row_end = csr->n_rows;
-  P.chunk_begin = 0;
-  P.pair_rows = pair_rows(csr);
-  P.nt_from = a->stream_from > 0 ? a->stream_from : 0x7fffffff;
-  P.nt_out_from = a->stream_out_from > 0 ? a->stream_out_from : 0x7fffffff;
-  hipStream_t st = as_stream(stream);
-  switch (d) {
-    case 64: return dispatch_bf16<64>(P, a->weight_mode, st);
-    case 128: return dispatch_bf16<128>(P, a->weight_mode, st);
-    default: return dispatch_bf16<256>(P, a->weight_mode, st);
-  }
+  return for_wide_width(d, [&](auto W) {
+    constexpr int D = decltype(W)::value;
+    return a->weight_mode == 1 ? launch_spmm_bf16<D, 1>(P, as_stream(stream))
+                               : launch_spmm_bf16<D, 0>(P, as_stream(stream));
+  });
 }
 
 // ---------------------------------------------------------------------------

@@ -976,28 +976,18 @@ extern "C" int bbgr_scatter_apply(int64_t n, int64_t n_dst, const void *plan, co
   }
   if (n == 0) return BBGR_OK;
   BBGR_REQUIRE(plan && src && dst, "bbgr_scatter_apply: null arrays");
-  BBGR_REQUIRE(aligned16(src) && aligned16(dst) && ldsrc >= d && lddst >= d &&
-                   (ldsrc & 3) == 0 && (lddst & 3) == 0 &&
-                   (!src2 || (aligned16(src2) && ldsrc2 >= d && (ldsrc2 & 3) == 0)),
+  BBGR_REQUIRE(ld_ok(src, ldsrc, d) && ld_ok(dst, lddst, d) && ld_ok(src2, ldsrc2, d),
                "bbgr_scatter_apply: tables must be 16-byte aligned, ld >= d, ld % 4 == 0");
-  hipStream_t st = as_stream(stream);
   const size_t a = align_up(4 * (size_t)n);
   const char *ws = static_cast<const char *>(plan);
   const unsigned *k2 = reinterpret_cast<const unsigned *>(ws + a);
   const int *v2 = reinterpret_cast<const int *>(ws + 3 * a);
   const unsigned grid = (unsigned)((n + 15) / 16);
-#define BBGR_SEGMENTS(DD)                                                                        \
-  hipLaunchKernelGGL(scatter_segments_kernel<DD>, dim3(grid), dim3(256), 0, st, (long)n, k2, v2, \
-                     src, (long)ldsrc, src2, (long)ldsrc2, dst, (long)lddst, (unsigned)n_dst)
-  switch (d) {
-    case 8: BBGR_SEGMENTS(8); break;
-    case 16: BBGR_SEGMENTS(16); break;
-    case 32: BBGR_SEGMENTS(32); break;
-    case 64: BBGR_SEGMENTS(64); break;
-    case 128: BBGR_SEGMENTS(128); break;
-    default: BBGR_SEGMENTS(256); break;
-  }
-#undef BBGR_SEGMENTS
+  for_width(d, [&](auto W) {
+    hipLaunchKernelGGL(scatter_segments_kernel<decltype(W)::value>, dim3(grid), dim3(256), 0,
+                       as_stream(stream), (long)n, k2, v2, src, (long)ldsrc, src2, (long)ldsrc2,
+                       dst, (long)lddst, (unsigned)n_dst);
+  });
   BBGR_LAUNCHED("scatter_segments_kernel");
   return BBGR_OK;
 }
@@ -1023,8 +1013,7 @@ extern "C" int bbgr_scatter_add_rows(int64_t n, const int64_t *idx, const float 
   }
   if (n == 0) return BBGR_OK;
   BBGR_REQUIRE(idx && src && dst, "bbgr_scatter_add_rows: null arrays");
-  BBGR_REQUIRE(aligned16(src) && aligned16(dst) && ldsrc >= d && lddst >= d &&
-                   (ldsrc & 3) == 0 && (lddst & 3) == 0,
+  BBGR_REQUIRE(ld_ok(src, ldsrc, d) && ld_ok(dst, lddst, d),
                "bbgr_scatter_add_rows: tables must be 16-byte aligned, ld >= d, ld % 4 == 0");
   size_t have = *workspace_bytes;
   const int rc = bbgr_scatter_plan(n, idx, n_dst, workspace, &have, stream);
@@ -1037,10 +1026,7 @@ extern "C" int bbgr_bpr(const bbgr_bpr_args *a, bbgr_stream_t stream) {
   BBGR_REQUIRE(a->batch >= 0, "bbgr_bpr: negative batch");
   if (a->batch == 0) return BBGR_OK;
   const int d = a->d;
-  if (!supported_width(d)) {
-    set_error("bbgr_bpr: embedding dim %d unsupported (8, 16, 32, 64, 128, 256)", d);
-    return BBGR_ERR_UNSUPPORTED;
-  }
+  if (!supported_width(d)) return unsupported_width("bbgr_bpr", d);
   BBGR_REQUIRE(a->users && a->pos && a->neg && a->uf && a->itf,
                "bbgr_bpr: null index/table");
   BBGR_REQUIRE(a->n_users > 0 && a->n_items > 0, "bbgr_bpr: n_users/n_items must be set");
@@ -1073,21 +1059,14 @@ extern "C" int bbgr_bpr(const bbgr_bpr_args *a, bbgr_stream_t stream) {
   P.scores = a->scores;
   const long lds[] = {P.lduf, P.ldif, P.ldue, P.ldie, P.ldguf, P.ldgif, P.ldgue, P.ldgie, P.ldc};
   const void *ptrs[] = {P.uf, P.itf, P.ue, P.ie, P.g_uf, P.g_if, P.g_ue, P.g_ie, P.contrib};
-  for (int k = 0; k < 9; ++k) {
-    if (!ptrs[k]) continue;
-    BBGR_REQUIRE(aligned16(ptrs[k]) && lds[k] >= d && (lds[k] & 3) == 0,
+  for (int k = 0; k < 9; ++k)
+    BBGR_REQUIRE(ld_ok(ptrs[k], lds[k], d),
                  "bbgr_bpr: tables must be 16-byte aligned with ld >= d, ld % 4 == 0");
-  }
   const unsigned grid = (unsigned)((a->batch + 15) / 16);
-  hipStream_t st = as_stream(stream);
-  switch (d) {
-    case 8: hipLaunchKernelGGL(bpr_kernel<8>, dim3(grid), dim3(256), 0, st, P); break;
-    case 16: hipLaunchKernelGGL(bpr_kernel<16>, dim3(grid), dim3(256), 0, st, P); break;
-    case 32: hipLaunchKernelGGL(bpr_kernel<32>, dim3(grid), dim3(256), 0, st, P); break;
-    case 64: hipLaunchKernelGGL(bpr_kernel<64>, dim3(grid), dim3(256), 0, st, P); break;
-    case 128: hipLaunchKernelGGL(bpr_kernel<128>, dim3(grid), dim3(256), 0, st, P); break;
-    default: hipLaunchKernelGGL(bpr_kernel<256>, dim3(grid), dim3(256), 0, st, P); break;
-  }
+  for_width(d, [&](auto W) {
+    hipLaunchKernelGGL(bpr_kernel<decltype(W)::value>, dim3(grid), dim3(256), 0,
+                       as_stream(stream), P);
+  });
   BBGR_LAUNCHED("bpr_kernel");
   return BBGR_OK;
 }
@@ -1465,10 +1444,7 @@ extern "C" int bbgr_ego_rows(int64_t B, int32_t d, const int64_t *cu, const int6
                              int64_t ldgu, float *g_i, int64_t ldgi, float scale,
                              int32_t *counts_u_out, bbgr_stream_t stream) {
   BBGR_REQUIRE(B >= 0 && 3 * B < (1LL << 31), "bbgr_ego_rows: bad batch");
-  if (!supported_width(d)) {
-    set_error("bbgr_ego_rows: embedding dim %d unsupported (8, 16, 32, 64, 128, 256)", d);
-    return BBGR_ERR_UNSUPPORTED;
-  }
+  if (!supported_width(d)) return unsupported_width("bbgr_ego_rows", d);
   if (B == 0) return BBGR_OK;
   BBGR_REQUIRE(cu && sp && sn && iu && ii && ue && ie && counts && g_u && g_i,
                "bbgr_ego_rows: null arrays");
@@ -1481,19 +1457,11 @@ extern "C" int bbgr_ego_rows(int64_t B, int32_t d, const int64_t *cu, const int6
   BBGR_LAUNCHED("ego_count_kernel");
   const dim3 g((unsigned)((3 * B + 15) / 16));
   const float inv_b = 1.0f / (float)B;
-#define BBGR_EGO_ROWS(DD)                                                                   \
-  hipLaunchKernelGGL(ego_rows_kernel<DD>, g, dim3(256), 0, st, (long)B, (const long *)iu, \
-                     (const long *)ii, ue, (long)ldue, ie, (long)ldie, dloss, inv_b, reg,   \
-                     counts, g_u, (long)ldgu, g_i, (long)ldgi, scale, counts_u_out)
-  switch (d) {
-    case 8: BBGR_EGO_ROWS(8); break;
-    case 16: BBGR_EGO_ROWS(16); break;
-    case 32: BBGR_EGO_ROWS(32); break;
-    case 64: BBGR_EGO_ROWS(64); break;
-    case 128: BBGR_EGO_ROWS(128); break;
-    default: BBGR_EGO_ROWS(256); break;
-  }
-#undef BBGR_EGO_ROWS
+  for_width(d, [&](auto W) {
+    hipLaunchKernelGGL(ego_rows_kernel<decltype(W)::value>, g, dim3(256), 0, st, (long)B,
+                       (const long *)iu, (const long *)ii, ue, (long)ldue, ie, (long)ldie, dloss,
+                       inv_b, reg, counts, g_u, (long)ldgu, g_i, (long)ldgi, scale, counts_u_out);
+  });
   BBGR_LAUNCHED("ego_rows_kernel");
   return BBGR_OK;
 }
@@ -1510,15 +1478,26 @@ extern "C" int bbgr_graph_rows(int64_t n, const int64_t *ids, int64_t n_rows, co
   return BBGR_OK;
 }
 
+// The bbgr_rows_* entries' arguments (`who`: the entry's name in the message;
+// `lists`: its index arrays are all given; n_dst: 0 where the entry has none).
+// The arrays may be NULL where n == 0: the entry returns before it launches.
+static int check_rows_call(const char *who, int64_t n, int64_t n_dst, int32_t d, bool lists,
+                           const float *src, int64_t ldsrc, const float *dst, int64_t lddst) {
+  BBGR_REQUIRE_IN(who,
+                  n >= 0 && n_dst >= 0 && d > 0 && (d & 3) == 0 && ldsrc >= d && lddst >= d &&
+                      (ldsrc & 3) == 0 && (lddst & 3) == 0,
+                  "bad sizes (d, ld multiples of 4, ld >= d)");
+  BBGR_REQUIRE_IN(who, n == 0 || (lists && src && dst && aligned16(src) && aligned16(dst)),
+                  "null or unaligned arrays");
+  return BBGR_OK;
+}
+
 extern "C" int bbgr_rows_copy(int64_t n, const int64_t *idx, const float *src,
                               int64_t ldsrc, float *dst, int64_t lddst, int32_t d,
                               bbgr_stream_t stream) {
-  BBGR_REQUIRE(n >= 0 && d > 0 && (d & 3) == 0 && ldsrc >= d && lddst >= d &&
-                   (ldsrc & 3) == 0 && (lddst & 3) == 0,
-               "bbgr_rows_copy: bad sizes (d, ld multiples of 4, ld >= d)");
-  if (n == 0) return BBGR_OK;
-  BBGR_REQUIRE(idx && src && dst && aligned16(src) && aligned16(dst),
-               "bbgr_rows_copy: null or unaligned arrays");
+  const int rc =
+      check_rows_call("bbgr_rows_copy", n, 0, d, idx != nullptr, src, ldsrc, dst, lddst);
+  if (rc != BBGR_OK || n == 0) return rc;
   hipLaunchKernelGGL(rows_copy_kernel, dim3((unsigned)((n + 15) / 16)), dim3(256), 0,
                      as_stream(stream), (long)n, (const long *)idx,
                      reinterpret_cast<const float4 *>(src), (long)ldsrc / 4,
@@ -1530,12 +1509,9 @@ extern "C" int bbgr_rows_copy(int64_t n, const int64_t *idx, const float *src,
 extern "C" int bbgr_rows_add_unique(int64_t n, const int64_t *idx, const float *src,
                                     int64_t ldsrc, float *dst, int64_t lddst, int32_t d,
                                     int64_t n_dst, bbgr_stream_t stream) {
-  BBGR_REQUIRE(n >= 0 && n_dst >= 0 && d > 0 && (d & 3) == 0 && ldsrc >= d && lddst >= d &&
-                   (ldsrc & 3) == 0 && (lddst & 3) == 0,
-               "bbgr_rows_add_unique: bad sizes (d, ld multiples of 4, ld >= d)");
-  if (n == 0) return BBGR_OK;
-  BBGR_REQUIRE(idx && src && dst && aligned16(src) && aligned16(dst),
-               "bbgr_rows_add_unique: null or unaligned arrays");
+  const int rc = check_rows_call("bbgr_rows_add_unique", n, n_dst, d, idx != nullptr, src, ldsrc,
+                                 dst, lddst);
+  if (rc != BBGR_OK || n == 0) return rc;
   hipLaunchKernelGGL(rows_add_unique_kernel, dim3((unsigned)((n + 15) / 16)), dim3(256), 0,
                      as_stream(stream), (long)n, (const long *)idx,
                      reinterpret_cast<const float4 *>(src), (long)ldsrc / 4,
@@ -1548,12 +1524,9 @@ extern "C" int bbgr_rows_add_slots(int64_t n, const int64_t *slot, const int32_t
                                    const int64_t *rows, const float *src, int64_t ldsrc,
                                    float *dst, int64_t lddst, int32_t d, int64_t n_dst,
                                    bbgr_stream_t stream) {
-  BBGR_REQUIRE(n >= 0 && n_dst >= 0 && d > 0 && (d & 3) == 0 && ldsrc >= d && lddst >= d &&
-                   (ldsrc & 3) == 0 && (lddst & 3) == 0,
-               "bbgr_rows_add_slots: bad sizes (d, ld multiples of 4, ld >= d)");
-  if (n == 0) return BBGR_OK;
-  BBGR_REQUIRE(slot && counts && rows && src && dst && aligned16(src) && aligned16(dst),
-               "bbgr_rows_add_slots: null or unaligned arrays");
+  const int rc = check_rows_call("bbgr_rows_add_slots", n, n_dst, d, slot && counts && rows, src,
+                                 ldsrc, dst, lddst);
+  if (rc != BBGR_OK || n == 0) return rc;
   hipLaunchKernelGGL(rows_add_slots_kernel, dim3((unsigned)((n + 15) / 16)), dim3(256), 0,
                      as_stream(stream), (long)n, (const long *)slot, counts, (const long *)rows,
                      reinterpret_cast<const float4 *>(src), (long)ldsrc / 4,
@@ -1565,12 +1538,9 @@ extern "C" int bbgr_rows_add_slots(int64_t n, const int64_t *slot, const int32_t
 extern "C" int bbgr_rows_gather(int64_t n, const int64_t *idx, const float *src,
                                 int64_t ldsrc, float *dst, int64_t lddst, int32_t d,
                                 bbgr_stream_t stream) {
-  BBGR_REQUIRE(n >= 0 && d > 0 && (d & 3) == 0 && ldsrc >= d && lddst >= d &&
-                   (ldsrc & 3) == 0 && (lddst & 3) == 0,
-               "bbgr_rows_gather: bad sizes (d, ld multiples of 4, ld >= d)");
-  if (n == 0) return BBGR_OK;
-  BBGR_REQUIRE(idx && src && dst && aligned16(src) && aligned16(dst),
-               "bbgr_rows_gather: null or unaligned arrays");
+  const int rc =
+      check_rows_call("bbgr_rows_gather", n, 0, d, idx != nullptr, src, ldsrc, dst, lddst);
+  if (rc != BBGR_OK || n == 0) return rc;
   hipLaunchKernelGGL(rows_gather_kernel, dim3((unsigned)((n + 15) / 16)), dim3(256), 0,
                      as_stream(stream), (long)n, (const long *)idx,
                      reinterpret_cast<const float4 *>(src), (long)ldsrc / 4,

@@ -358,6 +358,20 @@ def set_spmm_timer(t: SpmmTimer | None) -> None:
     _timer = t
 
 
+def _fill_epilogue(a, y, y_scale, y_scale_s, add, add_scale, add_scale_s, acc_in, acc_out,
+                   acc_scale, acc_scale_s, gamma, acc_mask, add_mask) -> None:
+    """The epilogue fields of bbgr_spmm_args, as spmm() and epilogue() take them."""
+    a.y, a.ldy = ptr(y), ld(y)
+    a.y_scale, a.y_scale_s = ptr(y_scale), y_scale_s
+    a.add, a.ldadd = ptr(add), ld(add)
+    a.add_scale, a.add_scale_s = ptr(add_scale), add_scale_s
+    a.acc_in, a.ldacc_in = ptr(acc_in), ld(acc_in)
+    a.acc_out, a.ldacc_out = ptr(acc_out), ld(acc_out)
+    a.acc_scale, a.acc_scale_s = ptr(acc_scale), acc_scale_s
+    a.gamma = gamma
+    a.acc_mask, a.add_mask = ptr(acc_mask), ptr(add_mask)
+
+
 def spmm(prod: Product, x: torch.Tensor, first: bool, *, y=None, y_scale=None,
          y_scale_s: float = 1.0, add=None, add_scale=None, add_scale_s: float = 1.0,
          acc_in=None, acc_out=None, acc_scale=None, acc_scale_s: float = 1.0,
@@ -409,14 +423,8 @@ def spmm(prod: Product, x: torch.Tensor, first: bool, *, y=None, y_scale=None,
         a.weight_mode, a.edge_val = 1, ptr(prod.first_layer_values())
     else:
         a.weight_mode = 0
-    a.y, a.ldy = ptr(y), ld(y)
-    a.y_scale, a.y_scale_s = ptr(y_scale), y_scale_s
-    a.add, a.ldadd = ptr(add), ld(add)
-    a.add_scale, a.add_scale_s = ptr(add_scale), add_scale_s
-    a.acc_in, a.ldacc_in = ptr(acc_in), ld(acc_in)
-    a.acc_out, a.ldacc_out = ptr(acc_out), ld(acc_out)
-    a.acc_scale, a.acc_scale_s = ptr(acc_scale), acc_scale_s
-    a.gamma = gamma
+    _fill_epilogue(a, y, y_scale, y_scale_s, add, add_scale, add_scale_s, acc_in, acc_out,
+                   acc_scale, acc_scale_s, gamma, acc_mask, add_mask)
     a.partial = ptr(prod.workspace(d))
     a.src_mask, a.row_mask = ptr(src_mask), ptr(row_mask)
     if tag_out is not None:
@@ -425,7 +433,6 @@ def spmm(prod: Product, x: torch.Tensor, first: bool, *, y=None, y_scale=None,
         if src_mask is None:
             raise ValueError("spmm: tagged indices stand for a src_mask; pass it too")
         a.src_tagged, a.src_mask = ptr(tagged), None
-    a.acc_mask, a.add_mask = ptr(acc_mask), ptr(add_mask)
     if row_list is not None:
         a.row_list, a.n_row_list = ptr(row_list), row_list.numel()
         if row_count is not None:
@@ -520,15 +527,8 @@ def epilogue(t: torch.Tensor, *, y=None, y_scale=None, y_scale_s: float = 1.0, a
     output row row_list[j]; `n_rows` = the output tables' row count)."""
     a = _lib.SpmmArgs()
     a.d = t.shape[1]
-    a.y, a.ldy = ptr(y), ld(y)
-    a.y_scale, a.y_scale_s = ptr(y_scale), y_scale_s
-    a.add, a.ldadd = ptr(add), ld(add)
-    a.add_scale, a.add_scale_s = ptr(add_scale), add_scale_s
-    a.acc_in, a.ldacc_in = ptr(acc_in), ld(acc_in)
-    a.acc_out, a.ldacc_out = ptr(acc_out), ld(acc_out)
-    a.acc_scale, a.acc_scale_s = ptr(acc_scale), acc_scale_s
-    a.gamma = gamma
-    a.acc_mask, a.add_mask = ptr(acc_mask), ptr(add_mask)
+    _fill_epilogue(a, y, y_scale, y_scale_s, add, add_scale, add_scale_s, acc_in, acc_out,
+                   acc_scale, acc_scale_s, gamma, acc_mask, add_mask)
     a.row_mask = ptr(row_mask)
     if row_list is not None:
         if n_rows is None:
