@@ -150,6 +150,22 @@ class RecommendArgs(ctypes.Structure):
     ]
 
 
+class RecommendBf16Args(RecommendArgs):
+    """bbgr_recommend_bf16_args (bbgr_recommend_bf16): bbgr_recommend_args with
+    uf / itf as bf16 tables."""
+
+
+class RecommendRescoreArgs(ctypes.Structure):
+    """bbgr_recommend_rescore_args (bbgr_recommend_rescore)."""
+    _fields_ = [
+        ("n_users", c_int64), ("users", c_void_p), ("n_user_rows", c_int64),
+        ("uf", c_void_p), ("lduf", c_int64), ("itf", c_void_p), ("ldif", c_int64),
+        ("d", c_int32), ("n_items", c_int32), ("k", c_int32), ("k_pre", c_int32),
+        ("cand", c_void_p), ("cand_score", c_void_p), ("n_max", c_void_p),
+        ("topk", c_void_p), ("topk_score", c_void_p), ("certified", c_void_p),
+    ]
+
+
 SLAS_VIEW = {None: 0, "early": 1, "late": 2}   # bbgr_slas_view
 
 
@@ -318,6 +334,10 @@ _SIGNATURES = {
     "bbgr_eval_lists": ([ctypes.POINTER(EvalArgs), _P, ctypes.POINTER(c_size_t), _P], c_int32),
     "bbgr_recommend": ([ctypes.POINTER(RecommendArgs), _P, ctypes.POINTER(c_size_t), _P],
                        c_int32),
+    "bbgr_recommend_bf16": ([ctypes.POINTER(RecommendBf16Args), _P, ctypes.POINTER(c_size_t), _P],
+                            c_int32),
+    "bbgr_row_norm_max": ([c_int64, c_int32, _P, c_int64, _P, _P], c_int32),
+    "bbgr_recommend_rescore": ([ctypes.POINTER(RecommendRescoreArgs), _P], c_int32),
     "bbgr_eval_draw_candidates": ([ctypes.POINTER(Pcg64State), c_int64, _P, _P, _P, _P, _P,
                                    c_int64, c_int32, _P], c_int32),
     "bbgr_nonempty_rows": ([c_int32, _P, _P, _P, _P, ctypes.POINTER(c_size_t), _P],

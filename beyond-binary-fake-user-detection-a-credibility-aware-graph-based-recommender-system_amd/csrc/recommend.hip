@@ -20,28 +20,9 @@
 //  - d = 256: 128 user components per lane do not fit beside the lists at two
 //    waves per SIMD, so that form runs 4 waves (128 users) per workgroup, one
 //    per SIMD, with the whole unified register file.
-#include "topk.h"
+#include "recommend.h"
 
 namespace bbgr {
-
-constexpr int REC_MAX_K = 128;
-
-struct RecParams {
-  long n_users;               // users in this launch
-  const long *users;
-  const int *ex_indptr, *ex_indices;   // nullable together
-  const unsigned char *item_mask;      // nullable, [n_items], nonzero = eligible
-  const float *uf, *itf;
-  long lduf, ldif;
-  int n_items;
-  int split_items;            // items per split (multiple of FULL_TILE)
-  int n_splits;
-  int cont;                   // 0 first pass, 1 continuation pass (reads the bound)
-  float *list_score;          // [n_users][n_splits][2][KM]
-  int *list_item;
-  float *bound_score;         // [n_users]: the last pair the previous pass emitted
-  int *bound_item;            //            (INT_MAX: the user has no items left)
-};
 
 // Threads / users per workgroup, items per LDS tile and per-lane candidate
 // buffer depth, per embedding dim (LDS: 2 tiles of TILE x (D+4) floats + CB x
@@ -81,7 +62,7 @@ __global__ __launch_bounds__(RecShape<D>::THREADS) void recommend_kernel(RecPara
   // user fragment: component h*H + s of user u, for s = 0..H-1
   float ub[H];
   {
-    const float4 *pu = reinterpret_cast<const float4 *>(P.uf + u * P.lduf + h * H);
+    const float4 *pu = reinterpret_cast<const float4 *>(static_cast<const float *>(P.uf) + u * P.lduf + h * H);
 #pragma unroll
     for (int s = 0; s < H / 4; ++s) {
       const float4 v = valid ? pu[s] : make_float4(0.f, 0.f, 0.f, 0.f);
@@ -146,7 +127,7 @@ __global__ __launch_bounds__(RecShape<D>::THREADS) void recommend_kernel(RecPara
       const int f = threadIdx.x + THREADS * j;
       const int row = f / (D / 4), c4 = f % (D / 4);
       const int it = i0 + row;
-      stage[j] = it < item_hi ? reinterpret_cast<const float4 *>(P.itf + (long)it * P.ldif)[c4]
+      stage[j] = it < item_hi ? reinterpret_cast<const float4 *>(static_cast<const float *>(P.itf) + (long)it * P.ldif)[c4]
                               : make_float4(0.f, 0.f, 0.f, 0.f);
     }
   };
@@ -272,88 +253,10 @@ __global__ __launch_bounds__(RecShape<D>::THREADS) void recommend_kernel(RecPara
   }
 }
 
-// Per user (one wave): merge the 2 * n_splits sorted lists into the next
-// `n` (<= KM) entries of the user's list, positions [pos0, pos0 + n) of k, and
-// leave the last merged pair as the next pass's bound.
-template <int KM>
-__global__ __launch_bounds__(256) void recommend_merge_kernel(RecParams P, long b0, int k,
-                                                              int pos0, int n, int *topk,
-                                                              float *topk_score) {
-  const long b = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int l = threadIdx.x & 63;
-  if (b >= P.n_users) return;   // wave-uniform
-  const int L = 2 * P.n_splits;
-  const long base = b * L * KM;
-  int p = 0;
-  float hs = -INFINITY;
-  int hi = INT_MAX;
-  if (l < L) {
-    hs = P.list_score[base + l * KM];
-    hi = P.list_item[base + l * KM];
-  }
-  for (int j = 0; j < n; ++j) {
-    float bs = hs;
-    int bi = hi, bl = l;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const float os = __shfl_xor(bs, o);
-      const int oi = __shfl_xor(bi, o);
-      const int ol = __shfl_xor(bl, o);
-      const bool take = os > bs || (os == bs && (oi < bi || (oi == bi && ol < bl)));
-      bs = take ? os : bs;
-      bi = take ? oi : bi;
-      bl = take ? ol : bl;
-    }
-    if (l == 0) {
-      const long o = (b0 + b) * k + pos0 + j;
-      topk[o] = bi == INT_MAX ? -1 : bi;
-      if (topk_score) topk_score[o] = bi == INT_MAX ? -INFINITY : bs;
-      if (j == n - 1) {
-        P.bound_score[b] = bi == INT_MAX ? -INFINITY : bs;
-        P.bound_item[b] = bi;
-      }
-    }
-    if (l == bl) {
-      ++p;
-      hs = p < KM ? P.list_score[base + l * KM + p] : -INFINITY;
-      hi = p < KM ? P.list_item[base + l * KM + p] : INT_MAX;
-    }
-  }
-}
-
 // ---------------------------------------------------------------------------
 // Host side
 // ---------------------------------------------------------------------------
-// List depth: the shallower list when it needs no more passes than the deeper.
-static int rec_km(int k) { return (k + 15) / 16 <= (k + 23) / 24 ? 16 : 24; }
-
 static int rec_users(int d) { return d == 256 ? RecShape<256>::USERS : RecShape<64>::USERS; }
-
-struct RecLayout {
-  size_t lscore, litem, bscore, bitem, total;
-  long batch, splits;
-  int km;
-};
-
-static RecLayout rec_layout(const bbgr_recommend_args *a, int cus) {
-  RecLayout L{};
-  L.batch = a->n_users < FULL_BATCH ? a->n_users : FULL_BATCH;
-  const size_t nb = (size_t)(L.batch > 0 ? L.batch : 1);   // (no users: a minimal layout)
-  L.splits = full_splits((long)nb, a->n_items, cus, rec_users(a->d));
-  L.km = rec_km(a->k);
-  const size_t n = nb * L.splits * 2 * L.km;
-  size_t off = 0;
-  L.lscore = off;
-  off = align_up(off + sizeof(float) * n);
-  L.litem = off;
-  off = align_up(off + sizeof(int) * n);
-  L.bscore = off;
-  off = align_up(off + sizeof(float) * nb);
-  L.bitem = off;
-  off = align_up(off + sizeof(int) * nb);
-  L.total = off;
-  return L;
-}
 
 template <int D, int KM>
 static int launch_recommend(const RecParams &P, hipStream_t st) {
@@ -367,94 +270,23 @@ static int launch_recommend(const RecParams &P, hipStream_t st) {
   return BBGR_OK;
 }
 
-template <int KM>
-static int launch_rec_merge(const RecParams &P, long b0, const bbgr_recommend_args *a, int pos0,
-                            hipStream_t st) {
-  const unsigned grid = (unsigned)((P.n_users + 3) / 4);
-  const int n = a->k - pos0 < KM ? a->k - pos0 : KM;
-  hipLaunchKernelGGL(recommend_merge_kernel<KM>, dim3(grid), dim3(256), 0, st, P, b0, a->k, pos0,
-                     n, a->topk, a->topk_score);
-  BBGR_LAUNCHED("recommend_merge_kernel");
-  return BBGR_OK;
-}
-
 }  // namespace bbgr
 
 using namespace bbgr;
 
 extern "C" int bbgr_recommend(const bbgr_recommend_args *a, void *workspace,
                               size_t *workspace_bytes, bbgr_stream_t stream) {
-  BBGR_REQUIRE(a, "bbgr_recommend: null args");
-  BBGR_REQUIRE(workspace_bytes, "bbgr_recommend: null workspace_bytes");
-  BBGR_REQUIRE(a->n_users >= 0, "bbgr_recommend: n_users < 0");
-  BBGR_REQUIRE(a->k >= 1 && a->k <= REC_MAX_K, "bbgr_recommend: k not in [1, 128]");
-  BBGR_REQUIRE(a->n_items > 0, "bbgr_recommend: n_items <= 0");
-  BBGR_REQUIRE(a->n_user_rows > 0, "bbgr_recommend: n_user_rows <= 0");
-  BBGR_REQUIRE((a->ex_indptr == nullptr) == (a->ex_indices == nullptr),
-               "bbgr_recommend: ex_indptr and ex_indices must be given together");
-  if (a->n_users > 0) {
-    BBGR_REQUIRE(a->users, "bbgr_recommend: null users");
-    BBGR_REQUIRE(a->uf, "bbgr_recommend: null uf");
-    BBGR_REQUIRE(a->itf, "bbgr_recommend: null itf");
-    BBGR_REQUIRE(a->topk, "bbgr_recommend: null topk");
-  }
-  BBGR_REQUIRE(aligned16(a->uf) && (a->lduf & 3) == 0,
-               "bbgr_recommend: uf must be 16-byte aligned, lduf % 4 == 0");
-  BBGR_REQUIRE(aligned16(a->itf) && (a->ldif & 3) == 0,
-               "bbgr_recommend: itf must be 16-byte aligned, ldif % 4 == 0");
+  if (const int rc = rec_check_args("bbgr_recommend", a, workspace_bytes, 4)) return rc;
   const int d = a->d;
-  if (d != 64 && d != 128 && d != 256) {
-    set_error("bbgr_recommend: embedding dim %d unsupported (64, 128, 256)", d);
-    return BBGR_ERR_UNSUPPORTED;
-  }
-  BBGR_REQUIRE(a->n_users == 0 || (a->lduf >= d && a->ldif >= d),
-               "bbgr_recommend: lduf / ldif < d");
-  const RecLayout L = rec_layout(a, device_cus());
-  if (!workspace) {
-    *workspace_bytes = L.total;
-    return BBGR_OK;
-  }
-  if (*workspace_bytes < L.total) {
-    set_error("bbgr_recommend: workspace %zu < %zu bytes", *workspace_bytes, L.total);
-    return BBGR_ERR_WORKSPACE;
-  }
-  hipStream_t st = as_stream(stream);
-  char *ws = static_cast<char *>(workspace);
-  for (long b0 = 0; b0 < a->n_users; b0 += L.batch) {
-    RecParams P;
-    P.n_users = a->n_users - b0 < L.batch ? a->n_users - b0 : L.batch;
-    P.users = (const long *)a->users + b0;
-    P.ex_indptr = a->ex_indptr;
-    P.ex_indices = a->ex_indices;
-    P.item_mask = a->item_mask;
-    P.uf = a->uf;
-    P.itf = a->itf;
-    P.lduf = a->lduf;
-    P.ldif = a->ldif;
-    P.n_items = a->n_items;
-    P.n_splits = (int)L.splits;
-    const long per = (a->n_items + L.splits - 1) / L.splits;
-    P.split_items = (int)((per + FULL_TILE - 1) / FULL_TILE * FULL_TILE);
-    P.list_score = reinterpret_cast<float *>(ws + L.lscore);
-    P.list_item = reinterpret_cast<int *>(ws + L.litem);
-    P.bound_score = reinterpret_cast<float *>(ws + L.bscore);
-    P.bound_item = reinterpret_cast<int *>(ws + L.bitem);
-    for (int pos0 = 0; pos0 < a->k; pos0 += L.km) {
-      P.cont = pos0 > 0;
-      int rc;
-      switch (d * 100 + L.km) {
-        case 6416: rc = launch_recommend<64, 16>(P, st); break;
-        case 6424: rc = launch_recommend<64, 24>(P, st); break;
-        case 12816: rc = launch_recommend<128, 16>(P, st); break;
-        case 12824: rc = launch_recommend<128, 24>(P, st); break;
-        case 25616: rc = launch_recommend<256, 16>(P, st); break;
-        default: rc = launch_recommend<256, 24>(P, st); break;
-      }
-      if (rc) return rc;
-      rc = L.km == 16 ? launch_rec_merge<16>(P, b0, a, pos0, st)
-                      : launch_rec_merge<24>(P, b0, a, pos0, st);
-      if (rc) return rc;
-    }
-  }
-  return BBGR_OK;
+  return rec_run("bbgr_recommend", a, workspace, workspace_bytes, rec_users(d), stream,
+                 [d](const RecParams &P, int km, hipStream_t st) {
+                   switch (d * 100 + km) {
+                     case 6416: return launch_recommend<64, 16>(P, st);
+                     case 6424: return launch_recommend<64, 24>(P, st);
+                     case 12816: return launch_recommend<128, 16>(P, st);
+                     case 12824: return launch_recommend<128, 24>(P, st);
+                     case 25616: return launch_recommend<256, 16>(P, st);
+                     default: return launch_recommend<256, 24>(P, st);
+                   }
+                 });
 }

@@ -552,15 +552,17 @@ class FusedTrainer:
         return self._train_rows_csr
 
     def recommend(self, users, k: int, exclude_train: bool = True, item_mask=None,
-                  return_scores: bool = False):
+                  return_scores: bool = False, precision: str = "fp32", **kw):
         """The top-k items of `users` (input ids) under the current weights:
         forward(), then recommend.recommend on the final tables, the users'
         train items left out unless exclude_train=False. int32 [n, k] item
-        input ids (and float32 scores), -1 (-inf) past the eligible items."""
+        input ids (and float32 scores), -1 (-inf) past the eligible items.
+        precision (and prefilter_k / return_info) as recommend.recommend."""
         from .recommend import recommend
         uf, itf = self.forward()
         return recommend(uf, itf, users, k, exclude=self._train_rows() if exclude_train else None,
-                         item_mask=item_mask, return_scores=return_scores)
+                         item_mask=item_mask, return_scores=return_scores, precision=precision,
+                         **kw)
 
     def batch(self):
         """(users, pos, neg) of the last step, as input ids (int64)."""

@@ -1031,6 +1031,91 @@ int bbgr_recommend(const bbgr_recommend_args *args, void *workspace, size_t *wor
                    bbgr_stream_t stream);
 
 /* ------------------------------------------------------------------------- */
+/* bf16 recommendation lists, and exact fp32 lists by rescoring (opt-in;      */
+/* additions to ABI 12)                                                       */
+/*                                                                            */
+/* bbgr_recommend_bf16: bbgr_recommend on bf16 tables (bbgr_to_bf16's output: */
+/* 16-byte aligned, ld >= d, ld % 8 == 0 elements), every other field with    */
+/* its meaning above. A score is the fp32-accumulated product of the bf16     */
+/* rows (v_mfma_f32_32x32x16_bf16; products of two bf16 are exact in fp32);   */
+/* the lists are the exact top-k of THOSE scores, order (score desc, item     */
+/* asc), continuation passes and tie groups included. Same two-call workspace */
+/* idiom, same refusals; two launches over the same inputs give equal bits.   */
+/* ------------------------------------------------------------------------- */
+typedef struct {
+  int64_t n_users;
+  const int64_t *users;
+  int64_t n_user_rows;
+  const uint16_t *uf;
+  int64_t lduf;
+  const uint16_t *itf;
+  int64_t ldif;
+  int32_t d;
+  int32_t n_items;
+  int32_t k;
+  const int32_t *ex_indptr;
+  const int32_t *ex_indices;
+  const uint8_t *item_mask;
+  int32_t *topk;
+  float *topk_score;
+} bbgr_recommend_bf16_args;
+
+int bbgr_recommend_bf16(const bbgr_recommend_bf16_args *args, void *workspace,
+                        size_t *workspace_bytes, bbgr_stream_t stream);
+
+/* out[0] = an upper bound of max_r ||src[r, :]||_2 over the n_rows rows of   */
+/* an fp32 table (16-byte aligned, ld >= d, ld % 4 == 0; d a multiple of 4,   */
+/* 4 <= d <= 256): per row an fp32 sum of squares in a fixed order (at most   */
+/* 20 roundings), its square root, times 1 + 2^-20, plus 2^-58 for squares    */
+/* that underflow: never below the true norm, and at most the true norm times */
+/* 1 + 2^-19 plus 2^-58.                                                      */
+/* A row holding a NaN gives NaN. On the device: no host read, no float       */
+/* atomic (an integer max of the non-negative bit patterns: any order gives   */
+/* the same bits). n_rows == 0 writes 0.                                      */
+int bbgr_row_norm_max(int64_t n_rows, int32_t d, const float *src, int64_t ld, float *out,
+                      bbgr_stream_t stream);
+
+/* The fp32 top-k of each user among the k_pre candidates of a bf16 pass, and */
+/* the proof that it is the user's fp32 list.                                 */
+/*   cand / cand_score [n_users * k_pre]: bbgr_recommend_bf16's topk /        */
+/*     topk_score at k = k_pre over the bf16 roundings of uf / itf, with the  */
+/*     caller's exclusion and mask (-1 / -INFINITY in the tail of a row).     */
+/*   n_max: device scalar, an upper bound of max_i ||itf[i]||_2               */
+/*     (bbgr_row_norm_max). 1 <= k <= k_pre <= 128; d in {64, 128, 256}.      */
+/* Every candidate is scored with bbgr_recommend's fma chain (components 0,   */
+/* d/2, 1, d/2+1, ...), sorted (score desc, item asc); topk / topk_score      */
+/* (nullable) [n_users * k] take the first k, -1 / -INFINITY past the end.    */
+/* certified[b] = 1 when the row is proven to be bbgr_recommend's row, bit    */
+/* for bit: the norms are finite and at most 2^60, every candidate's fp32     */
+/* score is finite, and either the candidate row is not full (it holds every  */
+/* eligible item) or the k-th fp32 score is strictly greater than             */
+/* cand_score[k_pre - 1] + E_u, E_u = eps(d) * ||uf[u]|| * n_max plus the     */
+/* underflow terms 2^-121 (||uf[u]|| + n_max) + 2^-116, eps(d) = 1.02 * 2^-7  */
+/* + d * 2^-21 (the derivation is in csrc/recommend_bf16.hip). A row with     */
+/* certified[b] = 0 must be recomputed by bbgr_recommend. No workspace.       */
+typedef struct {
+  int64_t n_users;
+  const int64_t *users;
+  int64_t n_user_rows;
+  const float *uf;
+  int64_t lduf;
+  const float *itf;
+  int64_t ldif;
+  int32_t d;
+  int32_t n_items;
+  int32_t k;
+  int32_t k_pre;
+  const int32_t *cand;
+  const float *cand_score;
+  const float *n_max;
+  int32_t *topk;
+  float *topk_score;
+  uint8_t *certified;
+} bbgr_recommend_rescore_args;
+
+int bbgr_recommend_rescore(const bbgr_recommend_rescore_args *args, bbgr_stream_t stream);
+
+/* ------------------------------------------------------------------------- */
 /* SLAS subgraph sampling for the credibility GNN (added under ABI 12)        */
 /*   Replaces build_slas_subgraph and its helpers, main.py:727-883: a host    */
 /*   loop per seed user, per sampled item and per edge of every subgraph      */

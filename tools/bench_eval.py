@@ -32,6 +32,14 @@ cpu_baseline = the reference's per-user loop restated in oracle/ref_numpy.py
         config's degree law and item set (the tables keep the config's item
         count and --dim or the config's width); the listed users are those
         with test items. d = 256 has no eval_full arm (unsupported there).
+        In the same rounds: `recommend_bf16` (bbgr_recommend_bf16 on tables
+        converted once; the conversion is timed apart, `to_bf16_ms`) and
+        `recommend_bf16_exact`, the stages of precision="bf16_exact" with an
+        event between them: item-norm bound, bf16 pass at k_pre, rescoring,
+        and the fp32 fallback on the uncertified users (their share is
+        reported; its lists are checked against the fp32 arm's).
+        --trained-steps N takes the tables from a FusedTrainer run for N steps
+        on the train split instead of random ones.
 Prints ONE JSON line on stdout.
 """
 from __future__ import annotations
@@ -87,13 +95,26 @@ def bench_recommend(args):
     tr, te = split(edges, 0.2, 5)
     del edges
     trc, tec = Csr(tr[0], tr[1], U, I, dev), Csr(te[0], te[1], U, I, dev)
-    g = torch.Generator(device=dev).manual_seed(7)
-    uf = (torch.rand(U, d, device=dev, generator=g) - 0.5)
-    itf = (torch.rand(I, d, device=dev, generator=g) - 0.5)
+    if args.trained_steps:
+        from bbgr.graph import BipartiteGraph
+        from bbgr.trainer import FusedTrainer
+        trainer = FusedTrainer(BipartiteGraph(tr, U, I, dev), "v2_pop",
+                               cred=synthetic_credibility(U, 3), emb_dim=d,
+                               num_layers=cfg["num_layers"], batch_size=cfg["batch"])
+        for _ in range(args.trained_steps):
+            trainer.step()
+        uf, itf = (t.detach().clone() for t in trainer.forward())
+        del trainer
+    else:
+        g = torch.Generator(device=dev).manual_seed(7)
+        uf = (torch.rand(U, d, device=dev, generator=g) - 0.5)
+        itf = (torch.rand(I, d, device=dev, generator=g) - 0.5)
     pop_t = torch.tensor(np.bincount(tr[1], minlength=I).astype(np.float32), device=dev)
     users = EV._eval_users(tec)
     n = users.numel()
-    log(f"[recommend] {args.config}: {n} listed users x {I} items, d {d}")
+    log(f"[recommend] {args.config}: {n} listed users x {I} items, d {d}, "
+        f"{'trained ' + str(args.trained_steps) + ' steps' if args.trained_steps else 'random'} "
+        f"tables")
     k, kl = args.k, args.k_long
     with_full = d in (64, 128) and k <= 32
     i32 = dict(dtype=torch.int32, device=dev)
@@ -103,15 +124,23 @@ def bench_recommend(args):
     ea = EV._args(users, trc, tec, uf, itf, I, (k,), pop_t, int(tr.shape[1]), groups, sums)
     ea.topk = topk_full.data_ptr()
 
-    def rec_args(kk):
+    def rec_args(kk, cls=_lib.RecommendArgs, tu=uf, ti=itf, scores=False):
         out = torch.empty(n * kk, **i32)
-        a = _lib.RecommendArgs()
+        a = cls()
         a.n_users, a.users, a.n_user_rows = n, users.data_ptr(), U
-        a.uf, a.lduf, a.itf, a.ldif = uf.data_ptr(), d, itf.data_ptr(), d
+        a.uf, a.lduf, a.itf, a.ldif = tu.data_ptr(), d, ti.data_ptr(), d
         a.d, a.n_items, a.k = d, I, kk
         a.ex_indptr, a.ex_indices = trc.indptr.data_ptr(), trc.indices.data_ptr()
         a.topk = out.data_ptr()
+        if scores:
+            sc = torch.empty(n * kk, dtype=torch.float32, device=dev)
+            a.topk_score = sc.data_ptr()
+            return a, out, sc
         return a, out
+
+    from bbgr.recommend import _bf16_table, default_prefilter_k
+    ufh, ith = _bf16_table(uf), _bf16_table(itf)
+    k_pre = args.prefilter_k or default_prefilter_k(args.k)
 
     arms = {}
     if with_full:
@@ -121,6 +150,10 @@ def bench_recommend(args):
     arms["recommend"] = ("bbgr_recommend", ra)
     rl, _long = rec_args(kl)
     arms["recommend_long"] = ("bbgr_recommend", rl)
+    rb, topk_bf16 = rec_args(k, _lib.RecommendBf16Args, ufh, ith)
+    arms["recommend_bf16"] = ("bbgr_recommend_bf16", rb)
+    rp, cand, cand_score = rec_args(k_pre, _lib.RecommendBf16Args, ufh, ith, scores=True)
+    arms["bf16_pass_k_pre"] = ("bbgr_recommend_bf16", rp)
     ws = {}
     for name, (fn, a) in arms.items():
         ws[name] = EV._run(fn, a, dev)   # sizes the workspace; first (warm-up) call
@@ -137,13 +170,55 @@ def bench_recommend(args):
         torch.cuda.synchronize()
         return e0.elapsed_time(e1)
 
+    # the other stages of precision="bf16_exact" (its bf16 pass is the arm above)
+    n_max = torch.empty(1, device=dev)
+    topk_ex = torch.empty(n * k, **i32)
+    score_ex = torch.empty(n * k, dtype=torch.float32, device=dev)
+    cert = torch.empty(n, dtype=torch.uint8, device=dev)
+    ra_ = _lib.RecommendRescoreArgs()
+    ra_.n_users, ra_.users, ra_.n_user_rows = n, users.data_ptr(), U
+    ra_.uf, ra_.lduf, ra_.itf, ra_.ldif = uf.data_ptr(), d, itf.data_ptr(), d
+    ra_.d, ra_.n_items, ra_.k, ra_.k_pre = d, I, k, k_pre
+    ra_.cand, ra_.cand_score, ra_.n_max = cand.data_ptr(), cand_score.data_ptr(), n_max.data_ptr()
+    ra_.topk, ra_.topk_score, ra_.certified = (topk_ex.data_ptr(), score_ex.data_ptr(),
+                                              cert.data_ptr())
+
+    def timed(f):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(s)
+        f()
+        e1.record(s)
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1)
+
+    fb_users = [0]
+
+    def exact_rest():
+        """(to_bf16, norm, rescore, fallback) ms; the lists land in topk_ex."""
+        t_conv = timed(lambda: (_bf16_table(uf), _bf16_table(itf)))
+        t_norm = timed(lambda: _lib.call("bbgr_row_norm_max", I, d, itf.data_ptr(), d,
+                                         n_max.data_ptr(), st))
+        t_res = timed(lambda: _lib.call("bbgr_recommend_rescore", ctypes.byref(ra_), st))
+        n_fb = n - int(cert.sum())
+        fb_users[0] = n_fb
+        t_fb = 0.0
+        if n_fb:
+            def fallback():
+                rows = torch.argsort(cert, stable=True)[:n_fb]
+                topk_ex.view(n, k)[rows] = recommend(uf, itf, users[rows], k, exclude=trc)
+            t_fb = timed(fallback)
+        return t_conv, t_norm, t_res, t_fb
+
     for _ in range(args.warmup):
         for name in arms:
             once(name)
+        exact_rest()
     ms = {name: [] for name in arms}
+    rest = []
     for _ in range(args.reps):   # the arms alternate inside every round
         for name in arms:
             ms[name].append(once(name))
+        rest.append(exact_rest())
     stat = {name: {"median_ms": float(np.median(v)), "min_ms": float(np.min(v)),
                    "max_ms": float(np.max(v))} for name, v in ms.items()}
     flops = 2.0 * n * I * d
@@ -175,6 +250,21 @@ def bench_recommend(args):
         line["recommend_over_eval_full_scorer_merge"] = rec / sm
         # same lists wherever no train item reaches eval_full's top-k (always, at these sizes)
         line["lists_equal_eval_full"] = bool(torch.equal(topk_full, topk_rec))
+    bf = stat["recommend_bf16"]["median_ms"]
+    conv, norm, res, fb = (float(np.median(v)) for v in zip(*rest))
+    pre = stat["bf16_pass_k_pre"]["median_ms"]
+    same = (topk_bf16.view(n, k) == topk_rec.view(n, k)).all(1).float().mean()
+    line["recommend_bf16"] = {"k": k, "ms": bf, "to_bf16_ms": conv, "x_faster_than_fp32": rec / bf,
+                              "x_faster_with_conversion": rec / (bf + conv),
+                              "rows_equal_fp32": float(same)}
+    line["recommend_bf16_exact"] = {
+        "k": k, "k_pre": k_pre, "ms": conv + norm + pre + res + fb,
+        "x_faster_than_fp32": rec / (conv + norm + pre + res + fb),
+        "split_ms": {"to_bf16": conv, "item_norm_max": norm, "bf16_pass": pre, "rescore": res,
+                     "fallback_fp32": fb},
+        "certified_share": 1.0 - fb_users[0] / n, "fallback_users": fb_users[0],
+        "lists_equal_fp32": bool(torch.equal(topk_ex, topk_rec))}
+    line["tables"] = f"trained {args.trained_steps} steps" if args.trained_steps else "random"
     chk = recommend(uf, itf, users[:4096], kl, exclude=trc)
     line["long_prefix_equals_short"] = bool(torch.equal(chk[:, :k],
                                                         topk_rec.view(n, k)[:4096]))
@@ -204,6 +294,11 @@ def main():
     ap.add_argument("--k", type=int, default=10, help="--recommend: the single-pass list length")
     ap.add_argument("--k-long", type=int, default=100,
                     help="--recommend: a list length that needs continuation passes")
+    ap.add_argument("--prefilter-k", type=int, default=0,
+                    help="--recommend: candidates of the bf16_exact arm (0 = the default rule)")
+    ap.add_argument("--trained-steps", type=int, default=0,
+                    help="--recommend: tables from a FusedTrainer run for N steps on the train "
+                         "split instead of random ones")
     args = ap.parse_args()
     if args.recommend:
         return bench_recommend(args)
