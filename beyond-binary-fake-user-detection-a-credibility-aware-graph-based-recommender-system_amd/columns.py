@@ -33,7 +33,7 @@ import torch.distributed as dist
 from ._lib import call, stream_handle
 from .bpr import bpr_args
 from .graph import BipartiteGraph
-from .trainer import FusedTrainer
+from .trainer import FusedTrainer, default_tables
 
 WIDTHS = (8, 16, 32, 64, 128, 256)
 
@@ -90,11 +90,7 @@ class ColumnShardedTrainer(FusedTrainer):
         graph = train_edges if isinstance(train_edges, BipartiteGraph) else \
             BipartiteGraph(train_edges, num_users, num_items, dev, vertex_order=vertex_order)
         if u0 is None:   # FusedTrainer's full-width init (same stream on every rank)
-            g = torch.Generator(device="cpu").manual_seed(seed)
-            au = (6.0 / (num_users + emb_dim)) ** 0.5
-            ai = (6.0 / (num_items + emb_dim)) ** 0.5
-            u0 = (torch.rand(num_users, emb_dim, generator=g) * 2 - 1) * au
-            i0 = (torch.rand(num_items, emb_dim, generator=g) * 2 - 1) * ai
+            u0, i0 = default_tables(num_users, num_items, emb_dim, seed)
         u0 = torch.as_tensor(np.asarray(u0) if not isinstance(u0, torch.Tensor) else u0)
         i0 = torch.as_tensor(np.asarray(i0) if not isinstance(i0, torch.Tensor) else i0)
         super().__init__(graph, variant, cred=cred, emb_dim=self.c1 - self.c0,

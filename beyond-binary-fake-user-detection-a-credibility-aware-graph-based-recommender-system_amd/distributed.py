@@ -51,15 +51,14 @@ import torch
 import torch.distributed as dist
 
 from . import _lib
-from ._lib import OP_SYM, call, ld, ptr, stream_handle
+from ._lib import call, ld, ptr, stream_handle
 from .bpr import bpr_args
 from .graph import BipartiteGraph, Scales
 from .optim import AdamRows, adam_step
-from .propagate import (ORDER_GS, OperatorPair, backward, backward_steps, epilogue, forward,
+from .propagate import (ORDER_GS, backward, backward_steps, epilogue, forward,
                         forward_steps, spmm)
-from .sampler import PopMixSampler, nonempty_rows, shuffle
-from .scatter import RowScatter
-from .trainer import VARIANTS, FusedTrainer, _internal_rows, resolve_frontier
+from .sampler import shuffle
+from .trainer import FusedTrainer, _input_rows, default_tables
 
 
 def partition_users(deg_u: np.ndarray, world: int) -> np.ndarray:
@@ -482,21 +481,14 @@ class ShardedTrainer(FusedTrainer):
         item exchange sums fp32 partial rows; the bf16 forward is single-GPU)."""
         if forward_dtype != "fp32":
             raise ValueError("ShardedTrainer takes forward_dtype='fp32' only")
-        _lib.require_gpu()
-        if variant not in VARIANTS:
-            raise ValueError(f"unknown variant {variant!r}")
-        kind, order, mix_default = VARIANTS[variant]
+        dev = torch.device(device) if device is not None else torch.device("cuda")
+        kind, mix = self._init_model(variant, num_local_users, num_items, emb_dim, num_layers,
+                                     lr, reg, lambda_fair, seed, dev, forward_dtype, neg_mix_pop)
         self.group = group
         self.world = dist.get_world_size(group)
         self.rank = dist.get_rank(group)
-        dev = torch.device(device) if device is not None else torch.device("cuda")
-        self.device = dev
-        self.variant = variant
-        self.U, self.I, self.d, self.K = num_local_users, num_items, emb_dim, num_layers
         self.U_local = num_local_users
         self.lo, self.hi = user_offset, user_offset + num_local_users
-        self.order, self.lr, self.reg = order, lr, reg
-        self.lambda_fair, self.seed = lambda_fair, seed
         self.exchange = ItemExchange(group, exchange_parts, frontier_parts)
         # native_comm: True / "stream" = the item all-reduces through the C ABI's
         # own RCCL communicator on a comm stream; "inline" = every collective of
@@ -516,36 +508,18 @@ class ShardedTrainer(FusedTrainer):
             dist.all_reduce(g, op=dist.ReduceOp.SUM, group=group)
             return g.to(torch.int32)
 
-        self.graph = BipartiteGraph(local_edges, num_local_users, num_items, dev,
-                                    vertex_order=vertex_order, item_degree_hook=global_degrees)
-        indptr_i = global_item_indptr(self.graph.item_csr.degrees(), group)
+        graph = BipartiteGraph(local_edges, num_local_users, num_items, dev,
+                               vertex_order=vertex_order, item_degree_hook=global_degrees)
+        indptr_i = global_item_indptr(graph.item_csr.degrees(), group)
         self.exchange.balance_indptr = indptr_i
-        cred_t = None
-        if cred is not None and kind != OP_SYM:
-            cred_t = torch.as_tensor(np.asarray(cred, np.float32)).to(dev).contiguous()
-            cred_t = _internal_rows(self.graph.user_order, cred_t)
-        self.scales = _scales(kind, self.graph, indptr_i, cred_t)
-        self.pair = OperatorPair.factored(self.graph, self.scales)
+        # item scales from the GLOBAL item degrees
+        self._init_operator(graph, kind, cred, lambda c: _scales(kind, graph, indptr_i, c))
         self.chains = self._build_chains(int(column_chains), emb_dim, group, exchange_parts,
                                          frontier_parts, native_comm, indptr_i, dev)
-
-        f32 = dict(dtype=torch.float32, device=dev)
-        if u0 is None:   # rank-local stream for users, shared stream for items
-            gu = torch.Generator(device="cpu").manual_seed(seed + 104729 * (self.rank + 1))
-            gi = torch.Generator(device="cpu").manual_seed(seed)
-            au = (6.0 / (num_local_users * self.world + emb_dim)) ** 0.5
-            ai = (6.0 / (num_items + emb_dim)) ** 0.5
-            u0 = (torch.rand(num_local_users, emb_dim, generator=gu) * 2 - 1) * au
-            i0 = (torch.rand(num_items, emb_dim, generator=gi) * 2 - 1) * ai
-        self.user_w = torch.as_tensor(u0, dtype=torch.float32).to(dev).contiguous()
-        self.item_w = torch.as_tensor(i0, dtype=torch.float32).to(dev).contiguous()
-        if self.user_w.shape != (num_local_users, emb_dim) or self.item_w.shape != (num_items, emb_dim):
-            raise ValueError("initial tables have the wrong shape")
-        self.user_w = _internal_rows(self.graph.user_order, self.user_w)
-        self.item_w = _internal_rows(self.graph.item_order, self.item_w)
-        self.train_users = nonempty_rows(self.graph.user_csr)
-        if self.train_users.numel() == 0:
-            raise RuntimeError(f"rank {self.rank}: no train users in its shard")
+        # the popularity draw over the global item degrees; a stream per rank
+        self._init_batching(batch_size, None if mix <= 0 else _GlobalItemCsr(indptr_i), mix,
+                            neg_pop_gamma, neg_max_tries, seed + 7919 * self.rank,
+                            no_users=f"rank {self.rank}: no train users in its shard")
         # Every rank takes the same number of users per step (the all-gathers of
         # the batch's item rows need equal shapes), and no batch may hold a user
         # twice (the last forward user product updates acc rows in place from a
@@ -557,9 +531,10 @@ class ShardedTrainer(FusedTrainer):
         dist.all_reduce(n_min, op=dist.ReduceOp.MIN, group=group)
         self.B = self.B_local = max(1, min(int(batch_size), int(n_min.item())))
         self.B_global = self.B_local * self.world
-        z = lambda n: torch.zeros(n, emb_dim, **f32)  # noqa: E731
-        self.m_u, self.v_u = z(num_local_users), z(num_local_users)
-        self.fuse_adam = bool(fuse_adam) and order == ORDER_GS and num_layers >= 1
+        # one decision for every rank: the size rule on the GLOBAL edge count.
+        # The Jacobi order is not fused here, and the step keeps host scalars
+        # (dev_state None: it is not graph-captured).
+        self._init_step_state(frontier, int(indptr_i[-1]), fuse_adam, fuse_jacobi=False)
         # item ownership (module docstring): GS with the fused Adam only (the
         # Jacobi order reads the whole item weight table in its first user
         # product, and the unfused path keeps whole gradient tables)
@@ -567,32 +542,15 @@ class ShardedTrainer(FusedTrainer):
         self.item_bounds = owner_bounds(num_items, self.world)
         self.ia, self.ib = ((self.item_bounds[self.rank], self.item_bounds[self.rank + 1])
                             if self.own_items else (0, num_items))
-        self.m_i, self.v_i = z(self.ib - self.ia), z(self.ib - self.ia)
         self._items_stale = False   # some rows of item_w lag their owner's
-        self.uf, self.itf = z(num_local_users), z(num_items)
-        self.g_uf, self.g_if = z(num_local_users), z(num_items)   # all-zero between steps
-        self.g_u0, self.g_i0 = z(num_local_users), z(num_items)
-        B = self.B_local
-        self.parts = torch.empty(3 * B, **f32)
-        self.contrib = torch.empty(3 * B, emb_dim, **f32)
+        if u0 is None:   # rank-local stream for users, shared stream for items
+            u0, i0 = default_tables(num_local_users, num_items, emb_dim, seed,
+                                    user_seed=seed + 104729 * (self.rank + 1),
+                                    user_fan=num_local_users * self.world)
+        self._init_tables(u0, i0, self.B_local, item_moment_rows=self.ib - self.ia)
+        f32 = dict(dtype=torch.float32, device=dev)
         self.all_contrib = torch.empty(2 * self.B_global, emb_dim, **f32)
-        self.scatter = RowScatter()
-        self.loss = torch.zeros((), **f32)
         self.dloss = torch.full((), 1.0 / self.world, **f32)   # mean over the global batch
-        self.ws: dict = {}
-        self.pop = None
-        if lambda_fair != 0.0:
-            di = self.scales.deg_i
-            self.pop = (di / di.max().clamp(min=1.0)).contiguous()
-        mix = mix_default if neg_mix_pop is None else neg_mix_pop
-        self.sampler = PopMixSampler(self.graph.user_csr, None if mix <= 0 else _GlobalItemCsr(
-            indptr_i), num_items, mix_pop=mix, gamma=neg_pop_gamma if mix > 0 else None,
-            max_tries=neg_max_tries, seed=seed + 7919 * self.rank)
-        self.epoch, self.cursor, self.step_count = 0, 0, 0
-        self.perm = None
-        # one decision for every rank: the size rule on the GLOBAL edge count
-        self.frontier = resolve_frontier(frontier, int(indptr_i[-1]))
-        self.dev_state = None   # host step scalars (the sharded step is not graph-captured)
         # GS item Adam on a side stream beside the backward chain: its gradient
         # (gI/(K+1) + ego rows) is final once the all-gathered BPR rows are
         # summed, and with N > 1 the chain waits on its dense exchanges, so the
@@ -602,7 +560,7 @@ class ShardedTrainer(FusedTrainer):
         if overlap_item_adam is None:
             overlap_item_adam = self.world > 1
         self.overlap_item_adam = bool(overlap_item_adam) and self.fuse_adam
-        self.g_adam = z(num_items) if self.overlap_item_adam else None
+        self.g_adam = torch.zeros_like(self.g_if) if self.overlap_item_adam else None
         self._adam_stream = torch.cuda.Stream(device=dev) if self.overlap_item_adam else None
         # sparse frontier exchange: the step's global item frontier as a row list
         self.sparse_exchange = bool(sparse_exchange) and self.frontier
@@ -616,13 +574,15 @@ class ShardedTrainer(FusedTrainer):
         n_bounds = max(exchange_parts, frontier_parts) + 2
         # the first backward item product's slot bitmap (FusedTrainer): the
         # rank's batch users' edges in its item-CSR order, per front; full-width
-        # tables only (column chains run narrow kernels, which keep the mask)
-        self.slot_map = None
+        # tables only (column chains run narrow kernels, which keep the mask).
+        # The masks, slot_bits, item_list and item_count live per front (_use);
+        # of FusedTrainer's other frontier features the sharded step uses none:
+        # tagged, mask_i_bits, item_len and batch_fused stay off (_init_step_state).
         if self.frontier and emb_dim >= 64 and not self.chains:
             self.slot_map = self.graph.user_item_slots()
         n_bits = self.graph.item_csr.nnz // 32 + 4 if self.slot_map is not None else 0
-        self._fronts = [_Front(B, self.B_global, num_local_users, num_items, n_bounds, dev,
-                               n_bits) for _ in range(2)]
+        self._fronts = [_Front(self.B_local, self.B_global, num_local_users, num_items, n_bounds,
+                               dev, n_bits) for _ in range(2)]
         self._next = None
         self._list_ws = None
         self._list_need = None
@@ -638,13 +598,8 @@ class ShardedTrainer(FusedTrainer):
         deg_u = np.bincount(edges[0].astype(np.int64), minlength=num_users)
         bounds = partition_users(deg_u, world)
         lo, hi = int(bounds[rank]), int(bounds[rank + 1])
-        emb_dim = kw.get("emb_dim", 64)
         if u0 is None:   # the same global init on every rank; keep my rows
-            g = torch.Generator(device="cpu").manual_seed(seed)
-            au = (6.0 / (num_users + emb_dim)) ** 0.5
-            ai = (6.0 / (num_items + emb_dim)) ** 0.5
-            u0 = (torch.rand(num_users, emb_dim, generator=g) * 2 - 1) * au
-            i0 = (torch.rand(num_items, emb_dim, generator=g) * 2 - 1) * ai
+            u0, i0 = default_tables(num_users, num_items, kw.get("emb_dim", 64), seed)
         u0 = u0[lo:hi]
         c = None if cred is None else np.asarray(cred, np.float32)[lo:hi]
         tr = cls(shard_edges(edges, lo, hi), hi - lo, num_items, variant, cred=c,
@@ -879,7 +834,6 @@ class ShardedTrainer(FusedTrainer):
         self.sync_items()
         uf, itf = forward(self.pair, self.user_w, self.item_w, self.K, self.order, out_u=self.uf,
                           out_i=self.itf, ws=self.ws, reduce=self.exchange)
-        from .trainer import _input_rows
         return _input_rows(self.graph.user_order, uf), _input_rows(self.graph.item_order, itf)
 
     @_item_table_owner
@@ -977,13 +931,7 @@ class ShardedTrainer(FusedTrainer):
         else:
             backward(self.pair, self.g_uf, self.g_if, self.K, self.order, out_u=self.g_u0,
                      out_i=self.g_i0, ws=self.ws, reduce=self.exchange, grad_support=masks)
-            call("bbgr_rows_axpy", B, ptr(users), alpha, ptr(self.user_w), ld(self.user_w),
-                 ptr(self.g_u0), ld(self.g_u0), self.d, st)
-            call("bbgr_rows_axpy", self.all_items.numel(), ptr(self.all_items), alpha,
-                 ptr(self.item_w), ld(self.item_w), ptr(self.g_i0), ld(self.g_i0), self.d, st)
-            self.step_count += 1
-            adam_step(self.user_w, self.g_u0, self.m_u, self.v_u, self.step_count, self.lr)
-            adam_step(self.item_w, self.g_i0, self.m_i, self.v_i, self.step_count, self.lr)
+            self._unfused_tail(users, (self.all_items,), alpha)
         call("bbgr_rows_zero", B, ptr(users), ptr(self.g_uf), ld(self.g_uf), self.d, st)
         call("bbgr_rows_zero", self.all_items.numel(), ptr(self.all_items), ptr(self.g_if),
              ld(self.g_if), self.d, st)
@@ -1047,14 +995,7 @@ class ShardedTrainer(FusedTrainer):
                 self.pair, self.g_uf[:, cs], self.g_if[:, cs], self.K, self.order,
                 out_u=self.g_u0[:, cs], out_i=self.g_i0[:, cs], ws=ch.ws, reduce=ch.exchange,
                 grad_support=masks))
-            st = stream_handle()
-            call("bbgr_rows_axpy", B, ptr(users), alpha, ptr(self.user_w), ld(self.user_w),
-                 ptr(self.g_u0), ld(self.g_u0), self.d, st)
-            call("bbgr_rows_axpy", self.all_items.numel(), ptr(self.all_items), alpha,
-                 ptr(self.item_w), ld(self.item_w), ptr(self.g_i0), ld(self.g_i0), self.d, st)
-            self.step_count += 1
-            adam_step(self.user_w, self.g_u0, self.m_u, self.v_u, self.step_count, self.lr)
-            adam_step(self.item_w, self.g_i0, self.m_i, self.v_i, self.step_count, self.lr)
+            self._unfused_tail(users, (self.all_items,), alpha)
             return
         done = self._item_adam_beside() if self.overlap_item_adam else None
         self.step_count += 1

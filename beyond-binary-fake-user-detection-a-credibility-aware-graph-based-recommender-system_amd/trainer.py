@@ -56,6 +56,22 @@ def resolve_frontier(frontier, nnz: int) -> bool:
     return bool(frontier)
 
 
+def default_tables(U: int, I: int, d: int, seed: int, user_seed: int | None = None,
+                   user_fan: int | None = None):
+    """The default initial tables (u0 [U, d], i0 [I, d], rows by input id):
+    xavier_uniform_ draws from a seeded CPU stream, users before items. The
+    seeded parity runs depend on these bits. user_seed / user_fan (sharded
+    weak scaling): the users from a stream of their own, bounded for user_fan
+    rows (the shard holds U of them)."""
+    gi = torch.Generator(device="cpu").manual_seed(seed)
+    gu = gi if user_seed is None else torch.Generator(device="cpu").manual_seed(user_seed)
+
+    def draw(n, fan, g):
+        return (torch.rand(n, d, generator=g) * 2 - 1) * (6.0 / (fan + d)) ** 0.5
+    u0 = draw(U, U if user_fan is None else user_fan, gu)
+    return u0, draw(I, I, gi)
+
+
 FORWARD_DTYPES = {"fp32": torch.float32, "bf16": torch.bfloat16}
 
 
@@ -76,6 +92,24 @@ class FusedTrainer:
                  neg_pop_gamma: float = 0.75, neg_max_tries: int = 50,
                  lambda_fair: float = 0.0, seed: int = 42, u0=None, i0=None,
                  frontier="auto", fuse_adam: bool = True, forward_dtype: str = "fp32"):
+        # The constructor is these steps, in this order; ShardedTrainer runs the
+        # shared ones around its own graph, scales and fronts. Every attribute a
+        # step method reads is assigned by one of them, in every trainer class.
+        kind, mix = self._init_model(variant, graph.num_users, graph.num_items, emb_dim,
+                                     num_layers, lr, reg, lambda_fair, seed, graph.device,
+                                     forward_dtype, neg_mix_pop)
+        self._init_operator(graph, kind, cred)
+        if u0 is None:
+            u0, i0 = default_tables(self.U, self.I, emb_dim, seed)
+        self._init_tables(u0, i0, batch_size)
+        self._init_batching(batch_size, graph.item_csr, mix, neg_pop_gamma, neg_max_tries, seed)
+        self._init_step_state(frontier, graph.item_csr.nnz, fuse_adam)
+        self._init_batch_buffers()
+
+    def _init_model(self, variant: str, U: int, I: int, emb_dim: int, num_layers: int,
+                    lr: float, reg: float, lambda_fair: float, seed: int, device,
+                    forward_dtype: str, neg_mix_pop: float | None):
+        """Model scalars and variant -> (operator kind, negative sampler mix)."""
         if forward_dtype not in FORWARD_DTYPES:
             raise ValueError(f"forward_dtype must be 'fp32' or 'bf16', got {forward_dtype!r}")
         if forward_dtype == "bf16" and emb_dim < 64:
@@ -84,70 +118,111 @@ class FusedTrainer:
         _lib.require_gpu()
         if variant not in VARIANTS:
             raise ValueError(f"unknown variant {variant!r}; one of {sorted(VARIANTS)}")
-        kind, order, mix_default = VARIANTS[variant]
-        self.graph, self.variant, self.order = graph, variant, order
-        self.U, self.I, self.d, self.K = graph.num_users, graph.num_items, emb_dim, num_layers
-        self.lr, self.reg, self.B = lr, reg, batch_size
-        self.lambda_fair, self.seed = lambda_fair, seed
-        dev = graph.device
-        self.device = dev
+        kind, self.order, mix_default = VARIANTS[variant]
+        self.variant, self.device = variant, device
+        self.U, self.I, self.d, self.K = U, I, emb_dim, num_layers
+        self.lr, self.reg, self.lambda_fair, self.seed = lr, reg, lambda_fair, seed
+        return kind, mix_default if neg_mix_pop is None else neg_mix_pop
+
+    def _init_operator(self, graph: BipartiteGraph, kind: int, cred, scales=None) -> None:
+        """The graph, its scales and the operator pair. `scales(cred)`: the
+        scales from the credibility by internal row (default: the graph's own)."""
+        self.graph = graph
         cred_t = None
         if cred is not None and kind != OP_SYM:
-            cred_t = torch.as_tensor(np.asarray(cred, np.float32)).to(dev).contiguous()
+            cred_t = torch.as_tensor(np.asarray(cred, np.float32)).to(self.device).contiguous()
             cred_t = _internal_rows(graph.user_order, cred_t)
-        self.scales = graph.scales(kind, cred_t)
+        self.scales = graph.scales(kind, cred_t) if scales is None else scales(cred_t)
         self.pair = OperatorPair.factored(graph, self.scales)
 
-        f32 = dict(dtype=torch.float32, device=dev)
-        if u0 is None:
-            g = torch.Generator(device="cpu").manual_seed(seed)
-            au = (6.0 / (self.U + emb_dim)) ** 0.5
-            ai = (6.0 / (self.I + emb_dim)) ** 0.5
-            u0 = (torch.rand(self.U, emb_dim, generator=g) * 2 - 1) * au
-            i0 = (torch.rand(self.I, emb_dim, generator=g) * 2 - 1) * ai
-        self.user_w = torch.as_tensor(u0, dtype=torch.float32).to(dev).contiguous()
-        self.item_w = torch.as_tensor(i0, dtype=torch.float32).to(dev).contiguous()
-        if self.user_w.shape != (self.U, emb_dim) or self.item_w.shape != (self.I, emb_dim):
+    def _init_tables(self, u0, i0, B: int, item_moment_rows: int | None = None) -> None:
+        """Weights (u0 / i0: rows by input id), Adam moments (the item ones with
+        item_moment_rows rows, default every item), gradient and scratch tables
+        for batches of B users."""
+        graph, d = self.graph, self.d
+        f32 = dict(dtype=torch.float32, device=self.device)
+        self.user_w = torch.as_tensor(u0, dtype=torch.float32).to(self.device).contiguous()
+        self.item_w = torch.as_tensor(i0, dtype=torch.float32).to(self.device).contiguous()
+        if self.user_w.shape != (self.U, d) or self.item_w.shape != (self.I, d):
             raise ValueError("initial tables have the wrong shape")
         # tables are given (and generated) by input id; held in the graph's order
         self.user_w = _internal_rows(graph.user_order, self.user_w)
         self.item_w = _internal_rows(graph.item_order, self.item_w)
-        z = lambda n: torch.zeros(n, emb_dim, **f32)  # noqa: E731
-        self.m_u, self.v_u, self.m_i, self.v_i = z(self.U), z(self.U), z(self.I), z(self.I)
-        self.uf = torch.empty(self.U, emb_dim, **f32)
-        self.itf = torch.empty(self.I, emb_dim, **f32)
+        z = lambda n: torch.zeros(n, d, **f32)  # noqa: E731
+        n_mi = self.I if item_moment_rows is None else item_moment_rows
+        self.m_u, self.v_u, self.m_i, self.v_i = z(self.U), z(self.U), z(n_mi), z(n_mi)
+        self.uf, self.itf = z(self.U), z(self.I)
         self.g_uf, self.g_if = z(self.U), z(self.I)         # all-zero between steps
-        self.g_u0 = torch.empty(self.U, emb_dim, **f32)
-        self.g_i0 = torch.empty(self.I, emb_dim, **f32)
-        self.parts = torch.empty(3 * batch_size, **f32)
+        self.g_u0, self.g_i0 = z(self.U), z(self.I)
+        self.parts = torch.empty(3 * B, **f32)
+        # deterministic BPR gradient: per-triple rows, then a fixed-order scatter
+        self.contrib = torch.empty(3 * B, d, **f32)
+        self.scatter = RowScatter()
         self.loss = torch.zeros((), **f32)
         self.ws: dict = {}
         self.pop = None
-        if lambda_fair != 0.0:   # lightgcn_cu.py:583-584: pop = deg_i / max(deg_i)
+        if self.lambda_fair != 0.0:   # lightgcn_cu.py:583-584: pop = deg_i / max(deg_i)
             di = self.scales.deg_i
             self.pop = (di / di.max().clamp(min=1.0)).contiguous()
-        mix = mix_default if neg_mix_pop is None else neg_mix_pop
-        self.sampler = PopMixSampler(graph.user_csr, graph.item_csr, self.I, mix_pop=mix,
+
+    def _init_batching(self, batch_size: int, item_csr, mix: float, neg_pop_gamma: float,
+                       neg_max_tries: int, sampler_seed: int,
+                       no_users: str = "No train users with interactions. "
+                                       "Check your threshold/split.") -> None:
+        """Batch size, the negative sampler (item_csr: the item degrees its
+        popularity draw uses) and the epoch state."""
+        graph = self.graph
+        self.B = batch_size
+        self.sampler = PopMixSampler(graph.user_csr, item_csr, self.I, mix_pop=mix,
                                      gamma=neg_pop_gamma if mix > 0 else None,
-                                     max_tries=neg_max_tries, seed=seed)
+                                     max_tries=neg_max_tries, seed=sampler_seed)
         self.train_users = nonempty_rows(graph.user_csr)
         if self.train_users.numel() == 0:
-            raise RuntimeError("No train users with interactions. Check your threshold/split.")
+            raise RuntimeError(no_users)
         self.epoch, self.cursor, self.step_count = 0, 0, 0
         self.perm = None
-        # pos and neg of a batch of B live in posneg[:B] / posneg[B:2B], so the
-        # item-gradient scatter takes one contiguous index vector
-        self.posneg = torch.empty(2 * batch_size, dtype=torch.int64, device=dev)
-        self.pos, self.neg = self.posneg[:batch_size], self.posneg[batch_size:]
-        # deterministic BPR gradient: per-triple rows, then a fixed-order scatter
-        self.contrib = torch.empty(3 * batch_size, emb_dim, **f32)
-        self.scatter = RowScatter()
+        self._last_users = None
+
+    def _init_step_state(self, frontier, nnz: int, fuse_adam: bool,
+                         fuse_jacobi: bool = True) -> None:
+        """What the step methods branch on: the frontier rule on `nnz` edges, the
+        fused optimizer, and every optional frontier feature switched off (the
+        constructor that uses one turns it on: _init_batch_buffers here,
+        ShardedTrainer's fronts)."""
         # Exact frontier sparsity: a step reads the final tables only at batch
         # rows, and its loss gradient is non-zero only there. Masks (1 byte per
         # node) restrict the last forward layer to the rows it feeds and let the
         # first backward products skip exact-zero source rows. Loss, gradients
         # and updates are bitwise identical to the dense step (tested).
-        self.frontier = resolve_frontier(frontier, graph.item_csr.nnz)
+        self.frontier = resolve_frontier(frontier, nnz)
+        # Fused optimizer (GS order): the user Adam runs inside the last backward
+        # product's epilogue and the item Adam reads gI/(K+1) straight from the
+        # sparse BPR gradient table (grad_scale), so neither weight-gradient
+        # table is written or re-read. g_u0 / g_i0 are then not materialised;
+        # fuse_adam=False keeps them (the gradient-parity tests read them).
+        self.fuse_adam = bool(fuse_adam) and (
+            (self.order == ORDER_GS and self.K >= 1)
+            or (fuse_jacobi and self.order == ORDER_J and self.K >= 2))
+        # device-resident step scalars (Adam t, sampler counter) for graph
+        # capture; None = host scalars in the kernel arguments (eager default)
+        self.dev_state: DeviceStepState | None = None
+        self.mask_u = self.mask_i = self.mask_i_bits = None
+        self.slot_map = self.slot_bits = self.tagged = None
+        self.item_list = self.item_count = self.item_len = None
+        self.batch_fused = self._fused_pending = self._tag_fresh = False
+        # built on first use (_item_grad_side, _train_rows)
+        self._g_item_side = self._train_rows_csr = None
+
+    def _init_batch_buffers(self) -> None:
+        """The single-GPU step's batch ids and frontier buffers (ShardedTrainer
+        keeps its own per _Front). BBGR_TAGGED, BBGR_MASK_BITS and
+        BBGR_BATCH_FUSED are read here, at construction."""
+        graph, dev, order = self.graph, self.device, self.order
+        emb_dim, num_layers = self.d, self.K
+        # pos and neg of a batch of B live in posneg[:B] / posneg[B:2B], so the
+        # item-gradient scatter takes one contiguous index vector
+        self.posneg = torch.empty(2 * self.B, dtype=torch.int64, device=dev)
+        self.pos, self.neg = self.posneg[:self.B], self.posneg[self.B:]
         self.mask_u = _lib.byte_mask(self.U, dev)
         # (whole 4-byte words: bbgr_mark_list sets the item bytes by word atomics)
         self.mask_i = _lib.byte_mask(self.I, dev)
@@ -158,7 +233,6 @@ class FusedTrainer:
         # step) lets it test 64 edges per load (bbgr_spmm_args.src_bits;
         # bitwise the mask's result). Full-width tables only (narrow column
         # shards keep the mask).
-        self.slot_map = self.slot_bits = None
         if self.frontier and emb_dim >= 64:
             self.slot_map = graph.user_item_slots()
             self.slot_bits = torch.zeros(graph.item_csr.nnz // 32 + 4, dtype=torch.int32,
@@ -177,21 +251,18 @@ class FusedTrainer:
         # Off by default: at C4 the reader drops 0.905 -> 0.770 ms but the
         # writer's 50M extra mask-byte loads cost the forward product +0.26 ms
         # (1.467 -> 1.723 ms; profiles/round6/r6e_tagged_ab.txt).
-        self.tagged = None
         uc = graph.user_csr
         if (self.frontier and order == ORDER_GS and num_layers >= 2 and emb_dim >= 64
-                and forward_dtype == "fp32"   # (the bf16 products write no tagged copy)
+                and self.forward_dtype == "fp32"   # (the bf16 products write no tagged copy)
                 and uc.nnz <= 24 * uc.n_rows and os.environ.get("BBGR_TAGGED", "0") == "1"):
             self.tagged = torch.empty(max(uc.nnz, 1), dtype=torch.int32, device=dev)
         # Frontier: the item mask also packed one bit per item after the
         # marking (bbgr_mask_pack) for the first backward user product's
         # per-edge test (bbgr_spmm_args.src_mask_bits; bitwise the byte test;
         # BBGR_MASK_BITS=0 keeps the bytes for A/B)
-        self.mask_i_bits = None
         if (self.frontier and num_layers >= 1
                 and os.environ.get("BBGR_MASK_BITS", "1") != "0"):
             self.mask_i_bits = torch.zeros(self.I // 32 + 1, dtype=torch.int32, device=dev)
-        self.item_list = self.item_count = self.item_len = None
         # GS frontier: the step's bookkeeping (masks, list, slot bits, and the
         # sparse gradient rows' reset) runs as one launch at each end of the
         # step (bbgr_batch_begin / bbgr_batch_end) instead of ~11 small ones;
@@ -199,23 +270,12 @@ class FusedTrainer:
         # launches for A/B).
         self.batch_fused = (self.frontier and order == ORDER_GS
                             and os.environ.get("BBGR_BATCH_FUSED", "1") != "0")
-        self._fused_pending = False
         if self.frontier and order == ORDER_GS:
             self.item_list = torch.empty(max(self.I, 1), dtype=torch.int64, device=dev)
             self.item_count = torch.zeros(1, dtype=torch.int64, device=dev)
             # a host wait for the list's length is free only behind the dense
             # forward layers (K >= 2); at K = 1 its consumer is the next launch
             self.item_len = ListLength(self.item_count, wait=num_layers >= 2)
-        # Fused optimizer (GS order): the user Adam runs inside the last backward
-        # product's epilogue and the item Adam reads gI/(K+1) straight from the
-        # sparse BPR gradient table (grad_scale), so neither weight-gradient
-        # table is written or re-read. g_u0 / g_i0 are then not materialised;
-        # fuse_adam=False keeps them (the gradient-parity tests read them).
-        self.fuse_adam = bool(fuse_adam) and (
-            (order == ORDER_GS and num_layers >= 1) or (order == ORDER_J and num_layers >= 2))
-        # device-resident step scalars (Adam t, sampler counter) for graph
-        # capture; None = host scalars in the kernel arguments (eager default)
-        self.dev_state: DeviceStepState | None = None
 
     def enable_device_state(self, max_steps: int = 1 << 20) -> None:
         """Keep the Adam step and the sampler counter on the device from now on
@@ -289,19 +349,7 @@ class FusedTrainer:
                      out_i=self.g_i0, ws=self.ws, grad_support=masks,
                      src_bits=self._bits(masks), frontier_list=self._flist(masks),
                      tagged=self._tagged(masks), item_mask_bits=self._mask_bits(masks))
-            # ego L2 term goes straight to the weight grads (Version-2:503-507):
-            # d/de0 reg*mean(|e0|^2) = 2*reg/B * e0 on every (u, pos, neg) row
-            call("bbgr_rows_axpy", B, ptr(users), alpha, ptr(self.user_w), ld(self.user_w),
-                 ptr(self.g_u0), ld(self.g_u0), self.d, st)
-            call("bbgr_rows_axpy", B, ptr(pos), alpha, ptr(self.item_w), ld(self.item_w),
-                 ptr(self.g_i0), ld(self.g_i0), self.d, st)
-            call("bbgr_rows_axpy", B, ptr(neg), alpha, ptr(self.item_w), ld(self.item_w),
-                 ptr(self.g_i0), ld(self.g_i0), self.d, st)
-            self.step_count += 1
-            adam_step(self.user_w, self.g_u0, self.m_u, self.v_u, self.step_count, self.lr,
-                      dev=self.dev_state)
-            adam_step(self.item_w, self.g_i0, self.m_i, self.v_i, self.step_count, self.lr,
-                      dev=self.dev_state)
+            self._unfused_tail(users, (pos, neg), alpha)
         # restore the all-zero invariant of the sparse gradient tables
         if self._fused_pending:   # (+ the masks, list, bits and item side table)
             self._fused_pending = False
@@ -316,12 +364,28 @@ class FusedTrainer:
             self._set_masks(users, pos, neg, 0)
         return self.loss
 
+    def _unfused_tail(self, users, item_rows, alpha: float) -> None:
+        """After an unfused backward: the ego L2 term goes straight to the weight
+        grads (Version-2:503-507: d/de0 reg*mean(|e0|^2) = 2*reg/B * e0 on every
+        (u, pos, neg) row; item_rows: the item index vectors, one launch each),
+        then both Adam steps."""
+        st = stream_handle()
+        for rows, w, g in [(users, self.user_w, self.g_u0)] + [
+                (r, self.item_w, self.g_i0) for r in item_rows]:
+            call("bbgr_rows_axpy", rows.numel(), ptr(rows), alpha, ptr(w), ld(w), ptr(g), ld(g),
+                 self.d, st)
+        self.step_count += 1
+        adam_step(self.user_w, self.g_u0, self.m_u, self.v_u, self.step_count, self.lr,
+                  dev=self.dev_state)
+        adam_step(self.item_w, self.g_i0, self.m_i, self.v_i, self.step_count, self.lr,
+                  dev=self.dev_state)
+
     def _batch_args(self, users, g: bool = False):
         """bbgr_batch_args over the trainer's own batch (posneg halves)."""
         B = users.numel()
         uc = self.graph.user_csr
-        bits = getattr(self, "slot_bits", None)
-        side = getattr(self, "_g_item_side", None) if g else None
+        bits = self.slot_bits
+        side = self._g_item_side if g else None
         a = _lib.BatchArgs()
         a.batch = B
         a.users, a.pos, a.neg = ptr(users), ptr(self.posneg), ptr(self.posneg) + 8 * B
@@ -388,7 +452,7 @@ class FusedTrainer:
                  before_last=before_last, reduce=reduce, adam_i=adam_i,
                  tagged=self._tagged(masks), item_mask_bits=self._mask_bits(masks))
         if side:   # the side table is all-zero between steps (bbgr_batch_end's rows)
-            if not getattr(self, "_fused_pending", False):
+            if not self._fused_pending:
                 call("bbgr_rows_zero", item_rows.numel(), ptr(item_rows), ptr(ga), ld(ga),
                      self.d, st)
         elif item_adam:
@@ -396,10 +460,9 @@ class FusedTrainer:
 
     def _item_grad_side(self) -> torch.Tensor:
         """The fused item Adam's gradient table [I, d], all-zero between steps."""
-        ga = getattr(self, "_g_item_side", None)
-        if ga is None:
-            ga = self._g_item_side = torch.zeros_like(self.g_if)
-        return ga
+        if self._g_item_side is None:
+            self._g_item_side = torch.zeros_like(self.g_if)
+        return self._g_item_side
 
     def _item_adam(self, item_rows, g, a_gl: float, gl: float) -> None:
         """GS item Adam: grad_i0 = gl * (gI + a_gl * i0[pos, neg]) (Version-2:
@@ -441,22 +504,22 @@ class FusedTrainer:
         B = users.numel()
         call("bbgr_mark_rows", B, ptr(users), value, ptr(self.mask_u), self.U, st)
         uc = self.graph.user_csr
-        lst = getattr(self, "item_list", None)
+        lst = self.item_list
         # pos and neg are one contiguous vector when they are the trainer's own
         # posneg halves (both marked by one launch)
         pn = (pos.data_ptr() == self.posneg.data_ptr()
               and neg.data_ptr() == self.posneg.data_ptr() + 8 * B)
         items = [(2 * B, ptr(self.posneg))] if pn else [(B, ptr(pos)), (B, ptr(neg))]
-        if value and pn and getattr(self, "batch_fused", False) and lst is not None:
+        if value and pn and self.batch_fused and lst is not None:
             _lib.check_word_padded(self.mask_i, self.I, "item mask")
             a = self._batch_args(users)
             call("bbgr_batch_begin", ctypes.byref(a), st)
             self._pack_item_mask()
-            if getattr(self, "item_len", None) is not None:
+            if self.item_len is not None:
                 self.item_len.publish()
-            # (the step's end restores all of it in one bbgr_batch_end; a
-            # subclass ending with _set_masks(..., 0) restores it just as well)
-            self._fused_pending = type(self)._step is FusedTrainer._step
+            # (the step's end restores all of it in one bbgr_batch_end; a caller
+            # ending with _set_masks(..., 0) restores it by the separate launches)
+            self._fused_pending = True
             return self.mask_u, self.mask_i
         if not value:
             self._fused_pending = False
@@ -466,7 +529,7 @@ class FusedTrainer:
             for n, p in items:
                 call("bbgr_mark_list", n, p, None, None, *li)
             call("bbgr_mark_list", B, ptr(users), ptr(uc.indptr), ptr(uc.indices), *li)
-            if getattr(self, "item_len", None) is not None:
+            if self.item_len is not None:
                 self.item_len.publish()
         else:
             for n, p in items:
@@ -476,48 +539,44 @@ class FusedTrainer:
                      value, ptr(self.mask_i), st)
             if lst is not None:
                 self.item_count.zero_()
-                if getattr(self, "item_len", None) is not None:
+                if self.item_len is not None:
                     self.item_len.invalidate()
         if value:
             self._pack_item_mask()
-        if getattr(self, "slot_bits", None) is not None:   # set / clear the batch's bits
+        if self.slot_bits is not None:   # set / clear the batch's bits
             call("bbgr_mark_slots", B, ptr(users), ptr(uc.indptr), ptr(self.slot_map),
                  ptr(self.slot_bits), value, st)
         return self.mask_u, self.mask_i
 
     def _pack_item_mask(self) -> None:
         """mask_i_bits = mask_i packed (every word rewritten: nothing to clear)."""
-        bits = getattr(self, "mask_i_bits", None)
-        if bits is not None:
-            call("bbgr_mask_pack", self.I, ptr(self.mask_i), ptr(bits), stream_handle())
+        if self.mask_i_bits is not None:
+            call("bbgr_mask_pack", self.I, ptr(self.mask_i), ptr(self.mask_i_bits),
+                 stream_handle())
 
     def _mask_bits(self, masks):
         """backward(item_mask_bits=...) when the masks are on."""
-        return getattr(self, "mask_i_bits", None) if masks is not None else None
+        return self.mask_i_bits if masks is not None else None
 
     def _tag(self, masks):
         """forward(tag=...): the tagged user-CSR index copy and the item mask."""
-        t = getattr(self, "tagged", None)
-        self._tag_fresh = masks is not None and t is not None and self.K >= 2
-        return (t, masks[1]) if self._tag_fresh else None
+        self._tag_fresh = masks is not None and self.tagged is not None and self.K >= 2
+        return (self.tagged, masks[1]) if self._tag_fresh else None
 
     def _tagged(self, masks):
-        """backward(tagged=...): the copy, only if this step's forward wrote it
-        (a subclass step that runs its own forward never reads a stale copy)."""
-        fresh, self._tag_fresh = getattr(self, "_tag_fresh", False), False
+        """backward(tagged=...): the copy, only if this step's forward wrote it."""
+        fresh, self._tag_fresh = self._tag_fresh, False
         return self.tagged if (fresh and masks is not None) else None
 
     def _bits(self, masks):
         """The slot bitmap for backward(src_bits=...) when the masks are on."""
-        return getattr(self, "slot_bits", None) if masks is not None else None
+        return self.slot_bits if masks is not None else None
 
     def _flist(self, masks):
         """(item row list, device count) for backward(frontier_list=...)."""
-        lst = getattr(self, "item_list", None)
-        if masks is None or lst is None:
+        if masks is None or self.item_list is None:
             return None
-        ll = getattr(self, "item_len", None)   # (a subclass may point item_count elsewhere)
-        return lst, ll if ll is not None and ll.count is self.item_count else self.item_count
+        return self.item_list, self.item_len if self.item_len is not None else self.item_count
 
     def forward(self):
         """Final (layer-mean) tables, rows by input id."""
@@ -539,7 +598,7 @@ class FusedTrainer:
         g = self.graph
         if g.user_order is None and g.item_order is None and g.user_csr.cols_sorted:
             return g.user_csr
-        if getattr(self, "_train_rows_csr", None) is None:
+        if self._train_rows_csr is None:
             uc = g.user_csr
             rows = torch.repeat_interleave(torch.arange(self.U, device=uc.indptr.device),
                                            uc.degrees().long())

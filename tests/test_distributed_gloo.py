@@ -188,3 +188,30 @@ def test_sharded_item_table_guard_raises_on_stale_rows():
     assert tr.item_w is t
     for name in ("step", "sync_items", "forward", "state_dict"):
         assert getattr(ShardedTrainer, name).__wrapped__ is not None
+
+
+@pytest.mark.parametrize("rank_local", [False, True])
+def test_default_tables_are_the_seeded_xavier_draws(rank_local):
+    """trainer.default_tables (the one copy of the default init every trainer
+    uses) against the formula written out here: xavier_uniform_ bounds
+    sqrt(6 / (n + d)) on draws from one seeded CPU generator, users before
+    items; the sharded weak-scaling variant draws the users from a stream of
+    their own, bounded for the global user count. Bit for bit."""
+    from bbgr.trainer import default_tables
+    U, I, d, seed, rank, world = 7, 5, 8, 42, 1, 4
+
+    def draw(n, fan, g):
+        return (torch.rand(n, d, generator=g) * 2 - 1) * (6 / (fan + d)) ** 0.5
+
+    g = torch.Generator(device="cpu").manual_seed(seed)
+    if rank_local:
+        user_seed = seed + 104729 * (rank + 1)
+        gu = torch.Generator(device="cpu").manual_seed(user_seed)
+        want = draw(U, U * world, gu), draw(I, I, g)
+        got = default_tables(U, I, d, seed, user_seed=user_seed, user_fan=U * world)
+    else:
+        want = draw(U, U, g), draw(I, I, g)
+        got = default_tables(U, I, d, seed)
+    for a, b in zip(got, want):
+        assert a.dtype == torch.float32 and a.shape == b.shape
+        assert a.numpy().tobytes() == b.numpy().tobytes()
