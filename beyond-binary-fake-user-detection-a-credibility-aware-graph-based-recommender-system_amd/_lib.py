@@ -215,6 +215,19 @@ class FeatUserArgs(ctypes.Structure):
     ]
 
 
+class SplitArgs(ctypes.Structure):
+    """bbgr_split_args (bbgr_split_edges)."""
+    _fields_ = [
+        ("n", c_int64), ("n_users", c_int32), ("n_items", c_int32),
+        ("user", c_void_p), ("item", c_void_p), ("positive", c_void_p),
+        ("rating", c_void_p), ("pos_threshold", c_float), ("hash32", c_void_p),
+        ("thr_train", c_uint64), ("thr_val", c_uint64),
+        ("user_map", c_void_p), ("item_map", c_void_p),
+        ("user_src", c_void_p), ("item_src", c_void_p),
+        ("edges", c_void_p), ("ld_edges", c_int64), ("counts", c_void_p),
+    ]
+
+
 class Pcg64State(ctypes.Structure):
     """bbgr_pcg64: numpy's PCG64 bit_generator.state (128-bit state and
     increment as two 64-bit halves, the buffered 32-bit output)."""
@@ -371,6 +384,9 @@ _SIGNATURES = {
     "bbgr_feat_users": ([ctypes.POINTER(FeatColumns), ctypes.POINTER(FeatUserArgs), _P,
                          ctypes.POINTER(c_size_t), _P], c_int32),
     "bbgr_feat_edges": ([ctypes.POINTER(FeatColumns), _P, c_int64, c_int64, _P, _P], c_int32),
+    "bbgr_md5_pair_hash": ([c_int64, _P, _P, _P, _P, c_int32, _P, _P, c_int32, _P, _P, _P],
+                           c_int32),
+    "bbgr_split_edges": ([ctypes.POINTER(SplitArgs), _P, ctypes.POINTER(c_size_t), _P], c_int32),
     # blueprint names, thin forms of the entry points above
     "bbgr_spmm_f32": ([ctypes.POINTER(CsrStruct), _P, c_int64, _P, c_int64, c_int32, _P, _P,
                        _P, c_float, _P], c_int32),

@@ -1325,6 +1325,65 @@ int bbgr_feat_edges(const bbgr_feat_columns *c, const float *item_x, int64_t ts_
                     int64_t ts_max, float *edge_attr, bbgr_stream_t stream);
 
 /* ------------------------------------------------------------------------- */
+/* The md5 train / val / test split of review records (build_graph_from_jsonl, */
+/* lighgcn_cu_pop.py:227-303). Appended; the ABI stays 12. Integer work only:  */
+/* two calls give the same bits.                                              */
+/* ------------------------------------------------------------------------- */
+/* hash32[e] = the first 32 bits of md5 over the bytes user_id[user[e]] + "|"  */
+/* + item_id[item[e]]: digest bytes 0..3 read big-endian, Python's             */
+/* int(hexdigest[:8], 16). An id table is a byte pool (UTF-8) and offsets      */
+/* [n_ids + 1] into it, offsets[0] = 0, non-decreasing, the last at most the   */
+/* pool's size; ids of any length (a loop over 64-byte blocks, standard md5    */
+/* padding with the 64-bit bit length). keep (nullable, [n]): a record with    */
+/* keep[e] == 0 is skipped and hash32[e] left as it was; so is a record whose  */
+/* id lies outside its table (the caller checks ids: bbgr.split does, before   */
+/* any launch). One launch, no workspace, no synchronisation.                  */
+int bbgr_md5_pair_hash(int64_t n, const int32_t *user, const int32_t *item,
+                       const uint8_t *user_data, const int64_t *user_offsets, int32_t n_users,
+                       const uint8_t *item_data, const int64_t *item_offsets, int32_t n_items,
+                       const uint8_t *keep, uint32_t *hash32, bbgr_stream_t stream);
+
+/* The split. A record is positive when positive[e] != 0 or, with positive     */
+/* NULL, when rating[e] >= pos_threshold (float32, exact; a NaN is not), and   */
+/* its ids lie inside [0, n_users) / [0, n_items). A positive record goes to   */
+/* train if hash32[e] < thr_train, to val if hash32[e] < thr_val, else to      */
+/* test (integer compares; thr_train <= thr_val <= 2^32).                      */
+/*   user_map [n_users], item_map [n_items]: the new id of an old id, numbered */
+/*     by first appearance among the positive records in file order; -1 for    */
+/*     an id with no positive record                                           */
+/*   user_src [U'], item_src [I']: the inverse lists, src[new] = old (room for */
+/*     n_users / n_items entries; only the first U' / I' are written)          */
+/*   edges [2, ld_edges] (ld_edges >= n): columns [0, E_train) train, then     */
+/*     E_val of val, then E_test of test, each in file order; row 0 the new    */
+/*     user ids, row 1 the new item ids; repeated pairs stay repeated; the     */
+/*     columns from E_train + E_val + E_test on are not written                */
+/*   counts (DEVICE int64 [5]) = {E_train, E_val, E_test, U', I'}              */
+/* Five launches and two memsets on `stream`; size query with workspace ==      */
+/* NULL (one byte per record and 20 bytes per tile of 2048 records).           */
+typedef struct {
+  int64_t n;                  /* records, < 2^31 - 1 */
+  int32_t n_users;            /* < 2^31 - 1 */
+  int32_t n_items;
+  const int32_t *user;        /* [n] */
+  const int32_t *item;        /* [n] */
+  const uint8_t *positive;    /* [n], nullable: then rating and pos_threshold */
+  const float *rating;        /* [n], read when positive == NULL */
+  float pos_threshold;
+  const uint32_t *hash32;     /* [n] */
+  uint64_t thr_train;
+  uint64_t thr_val;
+  int32_t *user_map;
+  int32_t *item_map;
+  int32_t *user_src;
+  int32_t *item_src;
+  int32_t *edges;
+  int64_t ld_edges;
+  int64_t *counts;
+} bbgr_split_args;
+int bbgr_split_edges(const bbgr_split_args *args, void *workspace, size_t *workspace_bytes,
+                     bbgr_stream_t stream);
+
+/* ------------------------------------------------------------------------- */
 /* Blueprint names (SURVEY §8(b)'s ABI sketch), thin forms of the above.      */
 /* ------------------------------------------------------------------------- */
 /* Y = diag(row_scale) A diag(col_scale) X (either scale NULL = ones), one    */
