@@ -228,6 +228,16 @@ class SplitArgs(ctypes.Structure):
     ]
 
 
+class TextArgs(ctypes.Structure):
+    """bbgr_text_args (bbgr_text_count, bbgr_text_unique)."""
+    _fields_ = [
+        ("n", c_int64), ("data", c_void_p), ("offsets", c_void_p),
+        ("first", c_int64), ("last", c_int64), ("hash_mask", c_uint64),
+        ("n_tokens", c_void_p), ("n_unique_tokens", c_void_p), ("recheck", c_void_p),
+        ("totals", c_void_p),
+    ]
+
+
 class Pcg64State(ctypes.Structure):
     """bbgr_pcg64: numpy's PCG64 bit_generator.state (128-bit state and
     increment as two 64-bit halves, the buffered 32-bit output)."""
@@ -387,6 +397,11 @@ _SIGNATURES = {
     "bbgr_md5_pair_hash": ([c_int64, _P, _P, _P, _P, c_int32, _P, _P, c_int32, _P, _P, _P],
                            c_int32),
     "bbgr_split_edges": ([ctypes.POINTER(SplitArgs), _P, ctypes.POINTER(c_size_t), _P], c_int32),
+    "bbgr_text_count": ([ctypes.POINTER(TextArgs), _P], c_int32),
+    "bbgr_text_unique": ([ctypes.POINTER(TextArgs), c_int64, _P, ctypes.POINTER(c_size_t), _P],
+                         c_int32),
+    "bbgr_text_unique_stages": ([ctypes.POINTER(TextArgs), c_int64, c_int32, _P,
+                                 ctypes.POINTER(c_size_t), _P], c_int32),
     # blueprint names, thin forms of the entry points above
     "bbgr_spmm_f32": ([ctypes.POINTER(CsrStruct), _P, c_int64, _P, c_int64, c_int32, _P, _P,
                        _P, c_float, _P], c_int32),

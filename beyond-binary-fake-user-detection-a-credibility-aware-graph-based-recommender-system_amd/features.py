@@ -10,8 +10,10 @@ graph pass (:423-570): ``user_x [U, 7]``, ``user_y [U]``, ``item_x [I, 2]``,
     g = SlasGraph((out.src, out.dst), out.edge_attr, out.user_x, out.user_y, out.item_x, "cuda")
 
 The device part starts at numeric per-review columns; the string work (JSON,
-id -> index maps, tokenising) is the one host pass of
-``review_columns_from_jsonl``.
+id -> index maps) is the one host pass of ``review_columns_from_jsonl``. The
+tokeniser runs in that pass by default (``tokens="host"``) or on the device
+(``tokens="device"``: the pass collects the encoded text and ``bbgr.text``
+counts the tokens; the columns are the same integers either way).
 
 A record is a review that has a user, an item and a rating: the records steps
 3 and 5 of the reference keep. Step 1 of the reference also counts, in
@@ -30,6 +32,7 @@ atomics: two calls give the same bits.
 from __future__ import annotations
 
 import ctypes
+import dataclasses
 import json
 import re
 from dataclasses import dataclass
@@ -48,6 +51,21 @@ USER_FEATURE_KEYS = ["Ru", "rating_entropy", "extremity_ratio", "average_rating_
 TAU_MS = 24 * 60 * 60 * 1000
 
 
+class _UnsetIsAbsent:
+    """The field ``ReviewColumns.text``: None by default, and kept out of the
+    instance's ``__dict__`` while it is None, so that callers who walk the
+    columns through ``cols.__dict__`` still meet arrays only."""
+
+    def __get__(self, obj, owner=None):
+        return None if obj is None else obj.__dict__.get("text")
+
+    def __set__(self, obj, value):
+        if value is None:
+            obj.__dict__.pop("text", None)
+        else:
+            obj.__dict__["text"] = value
+
+
 @dataclass
 class ReviewColumns:
     """One entry per record, in file order (numpy arrays, memory maps or
@@ -56,16 +74,18 @@ class ReviewColumns:
     ``timestamp`` int64 milliseconds, ``ts_valid`` an optional mask (False: the
     record has no timestamp; None: every record has one); ``n_tokens`` =
     len(tokenize(title + " " + text)) and ``n_unique_tokens`` = len(set(..)),
-    int32."""
+    int32, or both None and ``text`` the records' bytes (``bbgr.text.ReviewText``),
+    from which ``build_credibility_graph`` counts them on the device."""
     user: Any
     item: Any
     rating: Any
     helpful_vote: Any
     verified: Any
     timestamp: Any
-    n_tokens: Any
-    n_unique_tokens: Any
+    n_tokens: Any = None
+    n_unique_tokens: Any = None
     ts_valid: Any = None
+    text: Any = _UnsetIsAbsent()
 
     def __len__(self) -> int:
         return int(self.user.shape[0])
@@ -153,11 +173,18 @@ def build_credibility_graph(cols: ReviewColumns, num_users: int, num_items: int,
     buckets of the smallest and largest timestamp are 2^31 - 1 or more apart;
     ValueError naming timestamp when they span 2^53 ms or more.
     A user id with no record gets a NaN row of ``user_x`` and label -1; an
-    item id with no record mean 0 and count 0."""
+    item id with no record mean 0 and count 0. Without the two token columns
+    they are counted from ``cols.text`` (``bbgr.text.token_counts``); ValueError
+    when neither is given or ``text`` has another number of records."""
     device = torch.device(device)
     if device.type != "cuda":
         raise ValueError("build_credibility_graph runs on the GPU; there is no CPU fallback")
     U, I, E = int(num_users), int(num_items), len(cols)
+    if cols.n_tokens is None or cols.n_unique_tokens is None:
+        if cols.text is None:
+            raise ValueError("columns n_tokens / n_unique_tokens: give both, or text")
+        if len(cols.text) != E:
+            raise ValueError(f"text: expected {E} records, got {len(cols.text)}")
     if U < 0 or I < 0 or U >= 2**31 - 1 or I >= 2**31 - 1:
         raise ValueError("num_users and num_items must lie in [0, 2^31 - 1)")
     if E >= 2**31 - 1:
@@ -166,6 +193,10 @@ def build_credibility_graph(cols: ReviewColumns, num_users: int, num_items: int,
         _check_ids(cols.user, "user", U, "num_users")
         _check_ids(cols.item, "item", I, "num_items")
     _lib.require_gpu()
+    if cols.n_tokens is None or cols.n_unique_tokens is None:
+        from .text import token_counts
+        n_tok, n_uniq, _ = token_counts(cols.text, device)
+        cols = dataclasses.replace(cols, n_tokens=n_tok, n_unique_tokens=n_uniq)
     with torch.cuda.device(device):
         return _Pipeline(cols, U, I, E, torch.device("cuda", torch.cuda.current_device())).run()
 
@@ -281,11 +312,20 @@ def _as_int(x):
         return None
 
 
-def review_columns_from_jsonl(path, item_id_key: str = "parent_asin"):
+def review_columns_from_jsonl(path, item_id_key: str = "parent_asin", tokens: str = "host",
+                              device="cuda"):
     """One streaming pass over a review dump (one JSON object per line) ->
     ``(ReviewColumns, user2idx, item2idx)``. Records without a ``user_id``, an
     item id or a ``rating`` are skipped; ids are assigned in order of first
-    appearance among the kept records, as the reference's graph pass does."""
+    appearance among the kept records, as the reference's graph pass does.
+    ``tokens="host"`` tokenises every record in the pass; ``tokens="device"``
+    only encodes it and counts the tokens of all records on ``device``
+    afterwards (``bbgr.text.token_counts``): the same two columns, as device
+    tensors, and the bytes themselves in ``cols.text``."""
+    if tokens not in ("host", "device"):
+        raise ValueError(f"tokens = {tokens!r}: 'host' or 'device'")
+    on_device = tokens == "device"
+    encoded: list = []
     user2idx: dict = {}
     item2idx: dict = {}
     user, item, rating, helpful, verified, ts, ts_valid, n_tok, n_uniq = ([] for _ in range(9))
@@ -305,13 +345,23 @@ def review_columns_from_jsonl(path, item_id_key: str = "parent_asin"):
             t = _as_int(r.get("timestamp"))
             ts.append(0 if t is None else t)
             ts_valid.append(t is not None)
-            toks = tokenize(" ".join((r.get("title") or "", r.get("text") or "")))
+            s = " ".join((r.get("title") or "", r.get("text") or ""))
+            if on_device:
+                encoded.append(s.encode("utf-8", "surrogatepass"))
+                continue
+            toks = tokenize(s)
             n_tok.append(len(toks))
             n_uniq.append(len(set(toks)))
+    text = None
+    if on_device:
+        from .text import ReviewText, token_counts
+        text = ReviewText.from_encoded(encoded)
+        n_tok, n_uniq, _ = token_counts(text, device)
     cols = ReviewColumns(
         user=np.asarray(user, np.int32), item=np.asarray(item, np.int32),
         rating=np.asarray(rating, np.float32), helpful_vote=np.asarray(helpful, np.int32),
         verified=np.asarray(verified, np.uint8), timestamp=np.asarray(ts, np.int64),
-        n_tokens=np.asarray(n_tok, np.int32), n_unique_tokens=np.asarray(n_uniq, np.int32),
-        ts_valid=np.asarray(ts_valid, np.bool_))
+        n_tokens=n_tok if on_device else np.asarray(n_tok, np.int32),
+        n_unique_tokens=n_uniq if on_device else np.asarray(n_uniq, np.int32),
+        ts_valid=np.asarray(ts_valid, np.bool_), text=text)
     return cols, user2idx, item2idx

@@ -1,0 +1,214 @@
+"""Review text -> token and distinct-token counts, on the device.
+
+Restates, over the UTF-8 bytes of each record's ``title + " " + text``::
+
+    toks = re.findall(r"[a-z]+(?:'[a-z]+)?", s.lower())     # main.py tokenize()
+    n_tokens, n_unique_tokens = len(toks), len(set(toks))
+
+the two integers per record that ``build_credibility_graph`` turns into
+``lexical_diversity`` and ``review_length_discrepancy``::
+
+    text = ReviewText.from_strings(strings)
+    n_tokens, n_unique_tokens, info = token_counts(text)
+
+The rule over bytes: a letter is an ASCII ``A-Za-z`` compared as
+its lower case, or the byte ``C4`` of U+0130 (``İ``, whose ``lower()`` is ``i``
++ U+0307); ``'`` is the apostrophe; every other byte and a record's edge
+separate. With this Python's Unicode tables, U+0130 and U+212A (Kelvin sign,
+``lower()`` = ``k``) are the only code points outside ASCII whose ``lower()``
+holds a character of ``[a-z']`` (tests/test_text_host.py enumerates them).
+The Kelvin sign is the one letter that is not one byte: the device flags every
+record that holds it, and so every record in which two different tokens share
+a hash (none with the full 64 bits on any text seen so far; the comparison of
+the tokens' bytes on the device is what makes an unflagged record exact, not
+merely probable). Flagged records are counted again here on the host with
+``features.tokenize``.
+
+Launches per chunk: ``bbgr_text_count`` (one host read of the token total,
+which sizes the workspace), ``bbgr_text_unique``, one host read of the number
+of flagged records. Integer work only: two calls give the same bits.
+"""
+from __future__ import annotations
+
+import ctypes
+from typing import NamedTuple
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import call, ptr, stream_handle
+from .features import tokenize
+
+BYTES_MAX = 2**31 - 1     # a chunk's bytes and a call's records stay below this
+TEXT_STEP = 64            # bytes a wave reads per step (csrc/text.hip)
+
+
+class ReviewText(NamedTuple):
+    """The text of the records, in file order: ``data`` the UTF-8 bytes of
+    every record back to back (uint8), ``offsets`` int64 [n + 1] with record r
+    at ``data[offsets[r]:offsets[r + 1]]`` (numpy arrays or tensors; bytes
+    already on the GPU are used where they are)."""
+    data: object
+    offsets: object
+
+    def __len__(self) -> int:
+        return int(self.offsets.shape[0]) - 1
+
+    @classmethod
+    def from_strings(cls, strings) -> "ReviewText":
+        """``surrogatepass``: ``json.loads`` can return a lone surrogate, which a
+        plain encode refuses; its three bytes are separators like any others
+        of 0x80 and above."""
+        return cls.from_encoded([s.encode("utf-8", "surrogatepass") for s in strings])
+
+    @classmethod
+    def from_encoded(cls, enc: list) -> "ReviewText":
+        offsets = np.zeros(len(enc) + 1, np.int64)
+        if enc:
+            np.cumsum([len(b) for b in enc], out=offsets[1:])
+        return cls(np.frombuffer(bytearray().join(enc), np.uint8), offsets)   # writable: no copy later
+
+
+def _checked_text(text: ReviewText):
+    """(data, offsets): the offsets as host int64 after the checks; the bytes
+    as they came, a host array or, for a tensor on a GPU, that tensor (it is
+    not brought back to the host)."""
+    data = text.data
+    if isinstance(data, torch.Tensor):
+        if data.dtype != torch.uint8 or data.dim() != 1:
+            raise ValueError("text.data must be a uint8 vector")
+        data = data.contiguous() if data.is_cuda else data.numpy()
+    else:
+        data = np.asarray(data)
+    if not isinstance(data, torch.Tensor):
+        if data.dtype != np.uint8 or data.ndim != 1:
+            raise ValueError("text.data must be a uint8 vector")
+        data = np.ascontiguousarray(data)
+    off = (text.offsets.cpu().numpy() if isinstance(text.offsets, torch.Tensor)
+           else np.asarray(text.offsets))
+    if off.ndim != 1 or off.shape[0] < 1 or off.dtype != np.int64:
+        raise ValueError("text.offsets must be an int64 vector of n + 1 entries")
+    if off[0] < 0 or off[-1] > data.shape[0]:
+        raise ValueError(f"text.offsets span [{int(off[0])}, {int(off[-1])}], outside the "
+                         f"{data.shape[0]} bytes of data")
+    if off.shape[0] > 1 and bool((np.diff(off) < 0).any()):
+        raise ValueError("text.offsets must not decrease")
+    return data, np.ascontiguousarray(off)
+
+
+def _bytes_to(a, dev) -> torch.Tensor:
+    """A non-empty byte range on the device: one copy for a host array (a
+    read-only one, such as a memory map, is copied on the host first: torch
+    wants a writable one), none for a tensor that is there already."""
+    if isinstance(a, torch.Tensor):
+        return a.to(dev)
+    return torch.from_numpy(a if a.flags.writeable else a.copy()).to(dev)
+
+
+def _record_bytes(data, b0: int, b1: int) -> bytes:
+    a = data[b0:b1]
+    return (a.cpu().numpy() if isinstance(a, torch.Tensor) else a).tobytes()
+
+
+def plan_chunks(offsets: np.ndarray, chunk_bytes: int) -> list:
+    """[(r0, r1), ..]: consecutive record ranges that cover every record, each
+    of at most ``chunk_bytes`` bytes, taking as many records as fit; a record
+    longer than that is a range of its own. ValueError for a record of
+    2^31 - 1 bytes or more."""
+    chunk_bytes = int(chunk_bytes)
+    if chunk_bytes < 1:
+        raise ValueError("chunk_bytes must be at least 1")
+    chunk_bytes = min(chunk_bytes, BYTES_MAX - 1)
+    n = int(offsets.shape[0]) - 1
+    if n and int(np.diff(offsets).max()) >= BYTES_MAX:
+        r = int(np.diff(offsets).argmax())
+        raise ValueError(f"record {r} has {int(offsets[r + 1] - offsets[r])} bytes: a record "
+                         "must be shorter than 2^31 - 1 bytes")
+    chunks, r0 = [], 0
+    while r0 < n:
+        # the last r1 with offsets[r1] - offsets[r0] <= chunk_bytes
+        r1 = int(np.searchsorted(offsets, offsets[r0] + chunk_bytes, side="right")) - 1
+        r1 = min(max(r1, r0 + 1), n)
+        chunks.append((r0, r1))
+        r0 = r1
+    return chunks
+
+
+def _text_args(data: torch.Tensor, off: torch.Tensor, first: int, last: int, hash_mask: int,
+               n_tok: torch.Tensor, n_uniq: torch.Tensor, recheck: torch.Tensor,
+               totals: torch.Tensor) -> _lib.TextArgs:
+    a = _lib.TextArgs()
+    a.n, a.data, a.offsets = n_tok.numel(), ptr(data), ptr(off)
+    a.first, a.last, a.hash_mask = first, last, hash_mask
+    a.n_tokens, a.n_unique_tokens = ptr(n_tok), ptr(n_uniq)
+    a.recheck, a.totals = ptr(recheck), ptr(totals)
+    return a
+
+
+def _run_chunk(data: torch.Tensor, off: torch.Tensor, first: int, last: int, hash_mask: int,
+               n_tok: torch.Tensor, n_uniq: torch.Tensor, recheck: torch.Tensor,
+               totals: torch.Tensor) -> tuple:
+    """Both calls on device tensors: ``data`` the chunk's bytes (record r at
+    ``data[off[r]:off[r + 1]]``, ``first`` / ``last`` the host copies of
+    ``off[0]`` / ``off[-1]``), outputs [n]. Returns (tokens, flagged)."""
+    a = _text_args(data, off, first, last, hash_mask, n_tok, n_uniq, recheck, totals)
+    st = stream_handle()
+    call("bbgr_text_count", ctypes.byref(a), st)
+    tokens = int(totals[0])                                  # the host read that sizes the workspace
+    nb = _lib.workspace_query("bbgr_text_unique", ctypes.byref(a), tokens, args_after=(st,))
+    ws = torch.empty(max(nb, 1), dtype=torch.uint8, device=data.device)
+    call("bbgr_text_unique", ctypes.byref(a), tokens, ptr(ws), ctypes.byref(ctypes.c_size_t(nb)),
+         st)
+    return tokens, int(totals[1])
+
+
+def host_counts(record: bytes) -> tuple:
+    """(n_tokens, n_unique_tokens) of one record's bytes by ``features.tokenize``."""
+    toks = tokenize(record.decode("utf-8", "surrogatepass"))
+    return len(toks), len(set(toks))
+
+
+def token_counts(text: ReviewText, device="cuda", chunk_bytes: int = 1 << 30, _hash_mask: int = 0):
+    """``(n_tokens, n_unique_tokens, info)``: int32 [n] device tensors and
+    ``info = {"tokens", "rechecked", "chunks"}`` (the token total, the records
+    counted again on the host, the chunks run). The records go to the device
+    in chunks of at most ``chunk_bytes`` bytes (and below 2^31 - 1); a longer
+    record is a chunk of its own, and one of 2^31 - 1 bytes or more a
+    ValueError before any launch. ``_hash_mask`` narrows the hash (tests: it
+    forces collisions, which only raise ``rechecked``)."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise ValueError("token_counts runs on the GPU; there is no CPU fallback")
+    data, off = _checked_text(text)
+    n = off.shape[0] - 1
+    if n >= BYTES_MAX:
+        raise ValueError(f"n = {n} records: n must be < 2^31 - 1")
+    chunks = plan_chunks(off, chunk_bytes)
+    _lib.require_gpu()
+    with torch.cuda.device(device):
+        dev = torch.device("cuda", torch.cuda.current_device())
+        n_tok = torch.zeros(n, dtype=torch.int32, device=dev)
+        n_uniq = torch.zeros(n, dtype=torch.int32, device=dev)
+        recheck = torch.zeros(n, dtype=torch.uint8, device=dev)
+        totals = torch.zeros(2, dtype=torch.int64, device=dev)
+        flagged = 0
+        for r0, r1 in chunks:
+            b0, b1 = int(off[r0]), int(off[r1])
+            # the kernels read [0, b1 - b0) only; an empty chunk still needs an address
+            d = (_bytes_to(data[b0:b1], dev) if b1 > b0
+                 else torch.zeros(1, dtype=torch.uint8, device=dev))
+            o = torch.from_numpy(off[r0:r1 + 1] - b0).to(dev)
+            flagged += _run_chunk(d, o, 0, b1 - b0, int(_hash_mask), n_tok[r0:r1], n_uniq[r0:r1],
+                                  recheck[r0:r1], totals)[1]
+        if flagged:
+            idx = torch.nonzero(recheck).flatten()
+            fixed = np.empty((idx.numel(), 2), np.int32)
+            for k, r in enumerate(idx.tolist()):
+                fixed[k] = host_counts(_record_bytes(data, int(off[r]), int(off[r + 1])))
+            fixed_dev = torch.from_numpy(fixed).to(dev)
+            n_tok[idx] = fixed_dev[:, 0]
+            n_uniq[idx] = fixed_dev[:, 1]
+        info = {"tokens": int(n_tok.sum(dtype=torch.int64)), "rechecked": flagged,
+                "chunks": len(chunks)}
+        return n_tok, n_uniq, info

@@ -1384,6 +1384,67 @@ int bbgr_split_edges(const bbgr_split_args *args, void *workspace, size_t *works
                      bbgr_stream_t stream);
 
 /* ------------------------------------------------------------------------- */
+/* Token and distinct-token counts of review text (main.py tokenize():         */
+/* re.findall(r"[a-z]+(?:'[a-z]+)?", s.lower()), then len(toks) and            */
+/* len(set(toks))) over the UTF-8 bytes of the records. Appended; the ABI      */
+/* stays 12. Integer work only: two calls give the same bits.                  */
+/* ------------------------------------------------------------------------- */
+/* The rule over bytes: a letter is an ASCII A-Za-z (compared as lower case)   */
+/* or the byte C4 directly before B0 (U+0130: the letter i; B0 is a            */
+/* separator); 0x27 is the apostrophe; every other byte and a record's edge    */
+/* are separators. A maximal letter run is attached when exactly one           */
+/* apostrophe lies between it and the run before. A run begins a token unless  */
+/* it is attached and the run before it began one; then it is that token's     */
+/* apostrophe part. U+212A (E2 84 AA, lower() "k") is not handled on the       */
+/* device: bbgr_text_count sets recheck for every record that holds it.        */
+/* Record r is data[offsets[r], offsets[r + 1]); offsets are clamped into      */
+/* [first, last), and no byte outside that range is read as part of a token.   */
+typedef struct {
+  int64_t n;                 /* records, < 2^31 - 1 */
+  const uint8_t *data;       /* DEVICE: records back to back */
+  const int64_t *offsets;    /* DEVICE [n + 1], non-decreasing */
+  int64_t first, last;       /* HOST copies of offsets[0], offsets[n]; last - first < 2^31 - 1 */
+  uint64_t hash_mask;        /* 0: all 64 bits. Tests narrow it to force collisions */
+  int32_t *n_tokens;         /* [n] */
+  int32_t *n_unique_tokens;  /* [n] */
+  uint8_t *recheck;          /* [n] 1: the device does not vouch for this record */
+  int64_t *totals;           /* DEVICE int64 [2]: tokens, rechecks */
+} bbgr_text_args;
+/* n_tokens[r], recheck[r] (1 for a record that holds U+212A, else 0),         */
+/* totals[0] = the sum of n_tokens, totals[1] = 0. One wave per record walks   */
+/* it in steps of 64 bytes, a byte a lane (coalesced). One memset and one      */
+/* launch on `stream`; no workspace.                                           */
+int bbgr_text_count(const bbgr_text_args *args, bbgr_stream_t stream);
+/* n_unique_tokens[r], after bbgr_text_count on the same args (it reads        */
+/* n_tokens and adds to recheck). total_tokens: the host's copy of totals[0];  */
+/* it sizes the workspace (32 bytes per token, 4 per record, the sort's own)   */
+/* and is at most (last - first + n) / 2: a record of len bytes holds at most  */
+/* (len + 1) / 2 tokens, and a record's edge separates without a byte.         */
+/* Token offsets by a scan of n_tokens; per token its start and record; a      */
+/* 64-bit hash of its normalised bytes (FNV-1a and a finaliser, and-ed with    */
+/* hash_mask); a stable segmented radix sort by hash inside each record; then  */
+/* per sorted token: a new distinct token where the hash differs from the left */
+/* neighbour's, and with equal hashes a comparison of the two tokens'          */
+/* normalised bytes and lengths, whose failure sets recheck[r]. An unflagged   */
+/* record's count is therefore exact. totals[1] = the number of flagged        */
+/* records. Size query with workspace == NULL.                                 */
+int bbgr_text_unique(const bbgr_text_args *args, int64_t total_tokens, void *workspace,
+                     size_t *workspace_bytes, bbgr_stream_t stream);
+/* For measurement (tools/text_bench.py): the launch groups of                 */
+/* bbgr_text_unique picked by `stages`, on a workspace the groups before them  */
+/* have filled: EMIT the scan, the tokens' starts and hashes; SORT; VERIFY the */
+/* counts, the comparison and totals[1]. stages = 7 is bbgr_text_unique. A     */
+/* group run on a workspace its predecessors have not filled gives meaningless */
+/* counts but stays inside its buffers: offsets, records and token indices     */
+/* read from the workspace are clamped or checked before use.                  */
+#define BBGR_TEXT_STAGE_EMIT 1
+#define BBGR_TEXT_STAGE_SORT 2
+#define BBGR_TEXT_STAGE_VERIFY 4
+#define BBGR_TEXT_STAGE_ALL 7
+int bbgr_text_unique_stages(const bbgr_text_args *args, int64_t total_tokens, int32_t stages,
+                            void *workspace, size_t *workspace_bytes, bbgr_stream_t stream);
+
+/* ------------------------------------------------------------------------- */
 /* Blueprint names (SURVEY §8(b)'s ABI sketch), thin forms of the above.      */
 /* ------------------------------------------------------------------------- */
 /* Y = diag(row_scale) A diag(col_scale) X (either scale NULL = ones), one    */

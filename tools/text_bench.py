@@ -1,0 +1,283 @@
+"""Benchmark: review text -> token and distinct-token counts on MI355X.
+
+    python tools/text_bench.py [--records 1000000] [--reps 10] [--host-records N]
+                               [--jsonl-lines 200000] [--out profiles/text/text_c2.json]
+
+Workload: a seeded synthetic corpus of --records reviews (C2's record count by
+default): Zipf (1 / rank) draws from a vocabulary of 50,000 lower-case words
+of 2..11 letters, a Poisson number of tokens a record (mean 60), mixed case
+(lower, Capitalised, UPPER), separators of spaces, punctuation and apostrophes,
+about 2 % of them non-ASCII (accented letters, U+2019, U+0130, an emoji), and
+U+212A in about one record of 10,000 (the records the host counts again).
+
+Each launch group is timed alone with device events (median of --reps after
+--warmup) on device-resident text:
+
+  count   bbgr_text_count: the coalesced walk, n_tokens and the token total
+  emit    the scan of n_tokens, the tokens' starts and records, their hashes
+  sort    hipcub's segmented radix sort by hash inside each record
+  verify  distinct counts, the byte comparison of equal hashes, the recheck total
+
+`count` is set against the text bytes it has to read and the 8 TB/s of HBM.
+`call_ms` is one whole bbgr.text.token_counts from host memory (host clock: the
+host -> device copy, both host reads, the host recount of flagged records);
+`upload_ms` the copy alone (median of three after the first, `upload_first_ms`). The baseline is the parent's path: the
+bbgr.features.tokenize loop (findall, list, set) over the first --host-records
+records' strings on this machine's CPU (all of them by default); the device
+counts are compared with it record by record (`vs_host`). `jsonl` times
+bbgr.features.review_columns_from_jsonl in both modes on a dump of the first
+--jsonl-lines records. Prints ONE JSON line; writes --out.
+"""
+from __future__ import annotations
+
+import argparse
+import ctypes
+import json
+import os
+import statistics
+import sys
+import tempfile
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import bbgr  # noqa: E402,F401
+from bbgr import _lib  # noqa: E402
+from bbgr import features as FT  # noqa: E402
+from bbgr import text as TX  # noqa: E402
+
+HBM_PEAK = 8.0e12
+VOCAB, MEAN_TOKENS, BLOCK = 50_000, 60, 50_000
+# separator, weight: mostly spaces, some punctuation and apostrophes, a few non-ASCII
+SEPS = [(" ", 70), (", ", 6), (". ", 6), ("! ", 1), ("? ", 1), (" - ", 1), ("\n", 1), (" (", 1),
+        (") ", 1), ("'", 2), ("'s ", 2), ("' ", 1), (" '", 1), ("\u2019s ", 1.5), (" \u00e9 ", 1.5),
+        ("\u00fc", 1), (" \u0130", 1), (" \U0001F600 ", 1)]
+KELVIN_SEP = " \u212a "
+
+
+def log(*a):
+    print(*a, file=sys.stderr, flush=True)
+
+
+def _table(words: list) -> tuple:
+    """(bytes [n, width] zero padded, lengths [n]) of a list of byte strings."""
+    width = max(len(w) for w in words)
+    tab = np.zeros((len(words), width), np.uint8)
+    for k, w in enumerate(words):
+        tab[k, :len(w)] = np.frombuffer(w, np.uint8)
+    return tab, np.array([len(w) for w in words], np.int64)
+
+
+def synthetic_corpus(n_records: int, seed: int = 0) -> TX.ReviewText:
+    rng = np.random.default_rng(seed)
+    lengths = rng.integers(2, 12, VOCAB)
+    letters = rng.integers(97, 123, (VOCAB, 11), dtype=np.uint8)
+    vocab = np.where(np.arange(11)[None, :] < lengths[:, None], letters, 0).astype(np.uint8)
+    p = 1.0 / np.arange(1, VOCAB + 1)
+    cdf = np.cumsum(p / p.sum())
+    seps, sep_len = _table([s.encode("utf-8") for s, _ in SEPS] + [KELVIN_SEP.encode("utf-8")])
+    sep_p = np.array([w for _, w in SEPS], float)
+    sep_p /= sep_p.sum()
+    parts, offsets = [], [np.zeros(1, np.int64)]
+    end = 0
+    for r0 in range(0, n_records, BLOCK):
+        nr = min(BLOCK, n_records - r0)
+        per = rng.poisson(MEAN_TOKENS, nr)
+        T = int(per.sum())
+        w = np.minimum(np.searchsorted(cdf, rng.random(T)), VOCAB - 1)
+        case = rng.choice(3, T, p=[0.8, 0.15, 0.05])          # lower, Capitalised, UPPER
+        sep = rng.choice(len(SEPS), T, p=sep_p)
+        sep[rng.random(T) < 1.0 / (10_000 * MEAN_TOKENS)] = len(SEPS)
+        wl, sl = lengths[w], sep_len[sep]
+        tl = wl + sl
+        starts = np.cumsum(tl) - tl
+        total = int(tl.sum())
+        tok = np.repeat(np.arange(T), tl)
+        j = np.arange(total) - starts[tok]
+        in_word = j < wl[tok]
+        ch = np.where(in_word, vocab[w[tok], np.minimum(j, 10)],
+                      seps[sep[tok], np.clip(j - wl[tok], 0, seps.shape[1] - 1)])
+        upper = in_word & ((case[tok] == 2) | ((case[tok] == 1) & (j == 0)))
+        parts.append(np.where(upper, ch - 32, ch).astype(np.uint8))
+        rec_end = np.cumsum(per)                               # tokens before each record's end
+        tok_end = np.concatenate([[0], np.cumsum(tl)])
+        offsets.append(end + tok_end[rec_end])
+        end += total
+    return TX.ReviewText(np.concatenate(parts), np.concatenate(offsets).astype(np.int64))
+
+
+def timed_events(fn, warmup, reps):
+    for _ in range(warmup):
+        fn()
+    ts = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        ts.append(a.elapsed_time(b))
+    return {"median_ms": statistics.median(ts), "min_ms": min(ts), "max_ms": max(ts), "reps": reps}
+
+
+def strings_of(text: TX.ReviewText, n: int) -> list:
+    raw, off = text.data.tobytes(), text.offsets
+    return [raw[off[r]:off[r + 1]].decode("utf-8", "surrogatepass") for r in range(n)]
+
+
+def host_loop(strings: list) -> tuple:
+    """The parent's per-review steps: findall, list, set."""
+    n_tok, n_uniq = [], []
+    for s in strings:
+        toks = FT.tokenize(s)
+        n_tok.append(len(toks))
+        n_uniq.append(len(set(toks)))
+    return np.asarray(n_tok, np.int32), np.asarray(n_uniq, np.int32)
+
+
+def write_jsonl(path: str, strings: list, seed: int = 1) -> None:
+    rng = np.random.default_rng(seed)
+    n = len(strings)
+    users, items = rng.integers(0, max(n // 10, 1), n), rng.integers(0, max(n // 20, 1), n)
+    ratings, votes = rng.integers(1, 6, n), rng.integers(0, 5, n)
+    ts = 1_500_000_000_000 + rng.integers(0, 10**11, n)
+    with open(path, "w", encoding="utf-8") as f:
+        for k, s in enumerate(strings):
+            f.write(json.dumps({
+                "rating": float(ratings[k]), "title": s[:40], "text": s[40:],
+                "user_id": f"AE{int(users[k]):026d}", "parent_asin": f"B{int(items[k]):09d}",
+                "timestamp": int(ts[k]), "helpful_vote": int(votes[k]),
+                "verified_purchase": bool(k & 1)}) + "\n")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--records", type=int, default=1_000_000)
+    ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--host-records", type=int, default=None,
+                    help="records of the host baseline (default: all)")
+    ap.add_argument("--jsonl-lines", type=int, default=200_000)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("text_bench needs a GPU: no timing is taken without one")
+    out_path = args.out or os.path.join(ROOT, "profiles", "text", "text_c2.json")
+    t0 = time.perf_counter()
+    text = synthetic_corpus(args.records)
+    n, nbytes = len(text), int(text.data.shape[0])
+    log(f"corpus drawn in {time.perf_counter() - t0:.1f} s: {n} records, {nbytes} bytes")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    rec = {"records": n, "text_bytes": nbytes, "vocabulary": VOCAB,
+           "non_ascii_bytes": int((text.data >= 0x80).sum()),
+           "text_step": TX.TEXT_STEP, "device": torch.cuda.get_device_name(0),
+           "hbm_peak_TBps": HBM_PEAK / 1e12}
+
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    data = torch.from_numpy(text.data).to(dev)
+    off = torch.from_numpy(text.offsets).to(dev)
+    torch.cuda.synchronize()
+    rec["upload_first_ms"] = (time.perf_counter() - t0) * 1e3
+    ts = []
+    for _ in range(3):                       # the pages are touched now, as in call_ms below
+        t0 = time.perf_counter()
+        again = torch.from_numpy(text.data).to(dev)
+        torch.cuda.synchronize()
+        ts.append((time.perf_counter() - t0) * 1e3)
+    del again
+    rec["upload_ms"] = statistics.median(ts)
+
+    # the launch groups, on the buffers token_counts would make
+    n_tok = torch.zeros(n, dtype=torch.int32, device=dev)
+    n_uniq = torch.zeros(n, dtype=torch.int32, device=dev)
+    recheck = torch.zeros(n, dtype=torch.uint8, device=dev)
+    totals = torch.zeros(2, dtype=torch.int64, device=dev)
+    a = TX._text_args(data, off, 0, nbytes, 0, n_tok, n_uniq, recheck, totals)
+    st = _lib.stream_handle()
+    _lib.call("bbgr_text_count", ctypes.byref(a), st)
+    tokens = int(totals[0])
+    nb = _lib.workspace_query("bbgr_text_unique", ctypes.byref(a), tokens, args_after=(st,))
+    ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+    rec.update(device_tokens=tokens, tokens_per_record=tokens / max(n, 1), workspace_bytes=nb)
+
+    def stage(bits):
+        return lambda: _lib.call("bbgr_text_unique_stages", ctypes.byref(a), tokens, bits,
+                                 _lib.ptr(ws), ctypes.byref(ctypes.c_size_t(nb)), st)
+
+    groups = {"count": lambda: _lib.call("bbgr_text_count", ctypes.byref(a), st),
+              "emit": stage(1), "sort": stage(2), "verify": stage(4)}
+    kernels = {name: timed_events(fn, args.warmup, args.reps) for name, fn in groups.items()}
+    for name, r in kernels.items():
+        r["ns_per_token"] = r["median_ms"] * 1e6 / max(tokens, 1)
+        log(name, r)
+    c = kernels["count"]
+    c["text_TBps"] = nbytes / (c["median_ms"] * 1e-3) / 1e12
+    c["of_hbm_peak"] = c["text_TBps"] * 1e12 / HBM_PEAK
+    rec["kernels"] = kernels
+    rec["kernels_sum_ms"] = sum(r["median_ms"] for r in kernels.values())
+    rec["sort_share"] = kernels["sort"]["median_ms"] / rec["kernels_sum_ms"]
+    del ws
+
+    ts = []
+    for k in range(args.warmup + args.reps):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        d_tok, d_uniq, info = TX.token_counts(text, dev)
+        torch.cuda.synchronize()
+        if k >= args.warmup:
+            ts.append((time.perf_counter() - t0) * 1e3)
+    rec["call_ms"] = {"median_ms": statistics.median(ts), "min_ms": min(ts), "max_ms": max(ts),
+                      "reps": args.reps}
+    rec["info"] = info
+    log("call_ms", rec["call_ms"], info)
+
+    m = n if args.host_records is None else min(args.host_records, n)
+    strings = strings_of(text, m)
+    t0 = time.perf_counter()
+    h_tok, h_uniq = host_loop(strings)
+    host_s = time.perf_counter() - t0
+    rec["host_loop"] = {"records": m, "subset": "all" if m == n else f"the first {m}",
+                        "seconds": host_s, "us_per_record": host_s * 1e6 / max(m, 1),
+                        "tokens": int(h_tok.sum(dtype=np.int64))}
+    rec["vs_host"] = {
+        "records_compared": m,
+        "n_tokens": bool(np.array_equal(d_tok[:m].cpu().numpy(), h_tok)),
+        "n_unique_tokens": bool(np.array_equal(d_uniq[:m].cpu().numpy(), h_uniq)),
+        "rechecked": info["rechecked"]}
+    rec["call_vs_host_loop"] = host_s * (n / max(m, 1)) * 1e3 / rec["call_ms"]["median_ms"]
+    log("host_loop", rec["host_loop"], rec["vs_host"])
+
+    lines = min(args.jsonl_lines, m)
+    with tempfile.TemporaryDirectory() as td:
+        path = os.path.join(td, "reviews.jsonl")
+        write_jsonl(path, strings[:lines])
+        del strings
+        jl = {"lines": lines, "file_bytes": os.path.getsize(path)}
+        cols = {}
+        for mode in ("host", "device", "host", "device"):      # the second pair is reported
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            cols[mode] = FT.review_columns_from_jsonl(path, tokens=mode, device=dev)[0]
+            torch.cuda.synchronize()
+            jl[f"{mode}_s"] = time.perf_counter() - t0
+        jl["host_over_device"] = jl["host_s"] / jl["device_s"]
+        jl["columns_equal"] = bool(
+            np.array_equal(cols["host"].n_tokens, cols["device"].n_tokens.cpu().numpy())
+            and np.array_equal(cols["host"].n_unique_tokens,
+                               cols["device"].n_unique_tokens.cpu().numpy()))
+    rec["jsonl"] = jl
+    log("jsonl", jl)
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, "w") as f:
+        json.dump(rec, f, indent=1)
+        f.write("\n")
+    print(json.dumps(rec))
+
+
+if __name__ == "__main__":
+    main()
