@@ -215,6 +215,17 @@ class FeatUserArgs(ctypes.Structure):
     ]
 
 
+class FeatUserV2Args(ctypes.Structure):
+    """bbgr_feat_user_v2_args (bbgr_feat_users_v2)."""
+    _fields_ = [
+        ("u_indptr", c_void_p), ("u_eid", c_void_p), ("b_indptr", c_void_p),
+        ("b_bucket", c_void_p), ("item_mean", c_void_p), ("global_avg_lenlog", c_double),
+        ("group_tokens", c_void_p), ("group_unique", c_void_p), ("etg", c_void_p),
+        ("user_x", c_void_p), ("user_y", c_void_p), ("total_reviews", c_void_p),
+        ("helpful_reviews", c_void_p), ("user_extra", c_void_p),
+    ]
+
+
 class SplitArgs(ctypes.Structure):
     """bbgr_split_args (bbgr_split_edges)."""
     _fields_ = [
@@ -402,6 +413,18 @@ _SIGNATURES = {
                          c_int32),
     "bbgr_text_unique_stages": ([ctypes.POINTER(TextArgs), c_int64, c_int32, _P,
                                  ctypes.POINTER(c_size_t), _P], c_int32),
+    "bbgr_text_unique_pooled": ([ctypes.POINTER(TextArgs), c_int64, _P, c_int32, _P, _P, _P, _P,
+                                 ctypes.POINTER(c_size_t), _P], c_int32),
+    "bbgr_text_unique_pooled_stages": ([ctypes.POINTER(TextArgs), c_int64, _P, c_int32, _P, _P, _P,
+                                        c_int32, _P, ctypes.POINTER(c_size_t), _P], c_int32),
+    "bbgr_feat_lenlog": ([ctypes.POINTER(FeatColumns), _P, _P, ctypes.POINTER(c_size_t), _P],
+                         c_int32),
+    "bbgr_feat_item_means": ([ctypes.POINTER(FeatColumns), _P, _P, _P, _P,
+                              ctypes.POINTER(c_size_t), _P], c_int32),
+    "bbgr_feat_gaps": ([ctypes.POINTER(FeatColumns), _P, _P, _P, _P, ctypes.POINTER(c_size_t),
+                        _P], c_int32),
+    "bbgr_feat_users_v2": ([ctypes.POINTER(FeatColumns), ctypes.POINTER(FeatUserV2Args), _P,
+                            ctypes.POINTER(c_size_t), _P], c_int32),
     # blueprint names, thin forms of the entry points above
     "bbgr_spmm_f32": ([ctypes.POINTER(CsrStruct), _P, c_int64, _P, c_int64, c_int32, _P, _P,
                        _P, c_float, _P], c_int32),

@@ -22,44 +22,19 @@
 //
 // Measured at 1M and 50M records in DESIGN 4d (tools/features_bench.py).
 #include "common.h"
+#include "features.h"
 
 #include <limits.h>
 #include <math.h>
 
 namespace bbgr {
 
-constexpr int FEAT_LONG_ROW = 512;          // records; above: one workgroup per row
-constexpr int FEAT_LONG_GRID = 256;         // workgroups striding over the long-row list
 constexpr long long FEAT_TAU_MS = 86400000LL;   // one-day buckets (TAU_MS)
-
-// clamp(round_half_even(rating), 1, 5): Python's round() is half-to-even, as
-// rintf is in the default rounding mode. The clamp runs in float so that no
-// out-of-range value is converted; a NaN gives 1.
-__device__ __forceinline__ int feat_ri(float rating) {
-  return (int)fminf(fmaxf(rintf(rating), 1.f), 5.f);
-}
 
 __host__ __device__ __forceinline__ long long feat_floor_div(long long a, long long b) {
   long long q = a / b;
   if (a % b < 0) --q;   // b > 0: Python's //
   return q;
-}
-
-__device__ __forceinline__ bool feat_has_ts(const bbgr_feat_columns &C, long e) {
-  return C.ts_valid == nullptr || C.ts_valid[e] != 0;
-}
-
-// Sum over the 256 threads of a workgroup in a fixed order; every thread
-// returns the total. s: 4 entries of LDS, free again on return.
-template <typename T> __device__ __forceinline__ T feat_block_sum(T v, T *s) {
-#pragma clang fp contract(off)
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-  if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = v;
-  __syncthreads();
-  const T r = ((s[0] + s[1]) + s[2]) + s[3];
-  __syncthreads();
-  return r;
 }
 
 // ---------------------------------------------------------------------------
@@ -245,16 +220,6 @@ __device__ __forceinline__ void feat_user_acc(const bbgr_feat_columns &C,
     a.distinct += (p == bb || A.b_bucket[p] != A.b_bucket[p - 1]) ? 1 : 0;
 }
 
-__device__ __forceinline__ double feat_plogp(double H, int c, double n) {
-#pragma clang fp contract(off)
-  if (c > 0) {
-    const double p = (double)c / n;
-    const double t = p * log(p);
-    H -= t;
-  }
-  return H;
-}
-
 __device__ __forceinline__ void feat_user_store(const bbgr_feat_user_args &A, int u, int n,
                                                 int n_ts, const UserAcc &a) {
 #pragma clang fp contract(off)
@@ -371,53 +336,6 @@ __global__ __launch_bounds__(256) void feat_edges_kernel(bbgr_feat_columns C, co
         if (off + k < total) edge_attr[off + k] = s[4 * q + k];
     }
   }
-}
-
-static int feat_columns_ok(const char *fn, const bbgr_feat_columns *c) {
-#define FEAT_REQ(cond, what)                          \
-  do {                                                \
-    if (!(cond)) {                                    \
-      set_error("%s: %s", fn, what);                  \
-      return BBGR_ERR_INVALID;                        \
-    }                                                 \
-  } while (0)
-  FEAT_REQ(c, "null columns");
-  FEAT_REQ(c->n >= 0 && c->n < 2147483647LL, "n out of range (n must be < 2^31 - 1)");
-  FEAT_REQ(c->n_users >= 0 && c->n_users < INT_MAX, "n_users out of range");
-  FEAT_REQ(c->n_items >= 0, "n_items < 0");
-  if (c->n == 0) return BBGR_OK;
-  FEAT_REQ(c->n_users > 0 && c->n_items > 0, "records but no n_users / n_items");
-  FEAT_REQ(c->user, "null user");
-  FEAT_REQ(c->item, "null item");
-  FEAT_REQ(c->rating, "null rating");
-  FEAT_REQ(c->helpful_vote, "null helpful_vote");
-  FEAT_REQ(c->verified, "null verified");
-  FEAT_REQ(c->timestamp, "null timestamp");
-  FEAT_REQ(c->n_tokens, "null n_tokens");
-  FEAT_REQ(c->n_unique_tokens, "null n_unique_tokens");
-#undef FEAT_REQ
-  return BBGR_OK;
-}
-
-// Workspace of the two row passes: the long-row counter, then the list. A
-// long row has more than FEAT_LONG_ROW records, so there are fewer than
-// n / FEAT_LONG_ROW of them.
-static size_t feat_long_bytes(long n) {
-  return align_up(256 + sizeof(int) * (size_t)(n / FEAT_LONG_ROW + 1));
-}
-
-static int feat_workspace(const char *fn, size_t need, void *workspace, size_t *workspace_bytes,
-                          bool *query) {
-  *query = workspace == nullptr;
-  if (!workspace) {
-    *workspace_bytes = need;
-    return BBGR_OK;
-  }
-  if (*workspace_bytes < need) {
-    set_error("%s: workspace %zu < %zu bytes", fn, *workspace_bytes, need);
-    return BBGR_ERR_WORKSPACE;
-  }
-  return BBGR_OK;
 }
 
 }  // namespace bbgr

@@ -38,6 +38,7 @@
 // Integer work only; the integer atomics add order-free sums: two calls give
 // the same bits. Measured in DESIGN 4f (tools/text_bench.py).
 #include "common.h"
+#include "text.h"
 
 #include <hipcub/hipcub.hpp>
 #include <limits.h>
@@ -47,11 +48,6 @@ namespace bbgr {
 constexpr int TEXT_STEP = 64;          // bytes of a record one wave reads per step: a byte a lane
 constexpr int TEXT_WAVES = 4;          // records in flight per workgroup of 256 threads
 constexpr long TEXT_MAX_BLOCKS = 16384;
-
-__device__ __forceinline__ bool text_ascii_letter(unsigned b) {
-  const unsigned lo = b | 0x20u;   // A-Z onto a-z; no other byte lands inside a-z
-  return lo >= 'a' && lo <= 'z';
-}
 
 struct TextParams {
   long n;
@@ -67,16 +63,6 @@ struct TextParams {
   int *tok_rec;         // [total]
   long total;
 };
-
-// The record's byte range, clamped into [first, last): no offset, however
-// wrong, sends a read outside the text.
-__device__ __forceinline__ void text_range(const long long *offsets, long r, long first, long last,
-                                           long &beg, long &end) {
-  beg = (long)offsets[r];
-  end = (long)offsets[r + 1];
-  beg = beg < first ? first : beg;
-  end = end > last ? last : end;
-}
 
 template <bool EMIT>
 __global__ __launch_bounds__(64 * TEXT_WAVES) void text_walk_kernel(TextParams P) {
@@ -144,63 +130,6 @@ __global__ __launch_bounds__(64 * TEXT_WAVES) void text_walk_kernel(TextParams P
   }
   if (!EMIT && lane == 0 && wave_tokens)
     atomicAdd(reinterpret_cast<unsigned long long *>(P.totals), (unsigned long long)wave_tokens);
-}
-
-// A token read forward from its first byte: next() gives its normalised bytes
-// (lower-case letters, the apostrophe between its two parts) and -1 at its end.
-struct TokenCursor {
-  const uint8_t *d;
-  long q, end;
-  bool second;
-  __device__ __forceinline__ int letter(long at) const {
-    const unsigned b = d[at];
-    if (text_ascii_letter(b)) return (int)(b | 0x20u);
-    if (b == 0xC4u && at + 1 < end && d[at + 1] == 0xB0u) return 'i';
-    return 0;
-  }
-  __device__ __forceinline__ int next() {
-    if (q >= end) return -1;
-    const int c = letter(q);
-    if (c) {
-      ++q;
-      return c;
-    }
-    if (!second && d[q] == 0x27u && q + 1 < end && letter(q + 1)) {
-      second = true;
-      ++q;
-      return 0x27;
-    }
-    return -1;
-  }
-};
-
-struct TextTokens {
-  long n;
-  long total;   // the caller's count; the kernels stop at the scan's own, tok_off[n], if smaller
-  const uint8_t *data;
-  const long long *offsets;
-  long first, last;
-  const uint32_t *tok_pos;
-  const int *tok_rec;
-  const int *tok_off;
-  unsigned long long hash_mask;
-};
-
-__device__ __forceinline__ long text_live_tokens(const TextTokens &T) {
-  const long scanned = T.tok_off[T.n];
-  return scanned < T.total ? scanned : T.total;
-}
-
-// A slot or a record out of range (n_tokens changed between the two calls)
-// reads as an empty token.
-__device__ __forceinline__ TokenCursor text_cursor(const TextTokens &T, long tok) {
-  if (tok < 0 || tok >= T.total) return TokenCursor{T.data, 0, 0, false};
-  const int rec = T.tok_rec[tok];
-  if (rec < 0 || rec >= T.n) return TokenCursor{T.data, 0, 0, false};
-  long beg, end;
-  text_range(T.offsets, rec, T.first, T.last, beg, end);
-  long q = T.first + (long)T.tok_pos[tok];
-  return TokenCursor{T.data, q < end ? q : end, end, false};
 }
 
 __global__ __launch_bounds__(256) void text_hash_kernel(TextTokens T, unsigned long long *keys,
@@ -368,13 +297,9 @@ static int text_unique(const char *fn, const bbgr_text_args *a, int64_t total_to
         (const uint32_t *)nullptr, (uint32_t *)nullptr, T, (int)n, seg_b, seg_e, 0, 64,
         (hipStream_t) nullptr);
   }
-  const size_t off_rec = align_up(sizeof(int) * (size_t)(n + 1));
-  const size_t off_pos = off_rec + align_up(sizeof(int) * nt);
-  const size_t off_k1 = off_pos + align_up(sizeof(uint32_t) * nt);
-  const size_t off_k2 = off_k1 + align_up(sizeof(unsigned long long) * nt);
-  const size_t off_v1 = off_k2 + align_up(sizeof(unsigned long long) * nt);
-  const size_t off_v2 = off_v1 + align_up(sizeof(uint32_t) * nt);
-  const size_t off_tmp = off_v2 + align_up(sizeof(uint32_t) * nt);
+  const TextWorkspace W = text_workspace(n, nt);
+  const size_t off_rec = W.off_rec, off_pos = W.off_pos, off_k1 = W.off_k1, off_k2 = W.off_k2,
+               off_v1 = W.off_v1, off_v2 = W.off_v2, off_tmp = W.off_tmp;
   const size_t temp = t_scan > t_sort ? t_scan : t_sort;
   const size_t need = off_tmp + align_up(temp);
   if (!workspace) {

@@ -28,6 +28,16 @@ Launches of one call: ``bbgr_feat_stats`` (one host read of four integers),
 keyed by the id alone, and (user, day bucket) sorted), ``bbgr_feat_items``, ``bbgr_feat_users``,
 ``bbgr_feat_edges``. All sums run in double in a fixed order without float
 atomics: two calls give the same bits.
+
+``feature_set="v2"`` builds the later pipeline, main_v2_.py:291-524, for the
+same graph pass and model: columns 3 to 6 in its definitions (deviation from
+the item mean of the raw rating, the burst count over n, POOLED lexical
+diversity, the discrepancy of ``log1p`` lengths) and ``user_extra`` = (RNR,
+ETG) beside them. It needs ``cols.text`` (resident as one chunk, below
+2^31 - 1 bytes: ``bbgr.text.pooled_token_counts``; users it flags are counted
+again on the host) and adds ``bbgr_feat_lenlog``, ``bbgr_feat_item_means``,
+``bbgr_text_unique_pooled``, ``bbgr_feat_gaps`` and ``bbgr_feat_users_v2`` in
+``bbgr_feat_users``' place.
 """
 from __future__ import annotations
 
@@ -48,6 +58,8 @@ from ._lib import call, ptr, stream_handle
 EDGE_ATTR_KEYS = ["verified", "rating_align", "rating", "timestamp_norm", "helpful_vote"]
 USER_FEATURE_KEYS = ["Ru", "rating_entropy", "extremity_ratio", "average_rating_deviation",
                      "review_burst_count", "lexical_diversity", "review_length_discrepancy"]
+USER_EXTRA_KEYS = ["RNR", "ETG"]    # main_v2_.py:491-508, beside the seven
+FEATURE_SETS = ("main", "v2")
 TAU_MS = 24 * 60 * 60 * 1000
 
 
@@ -102,6 +114,22 @@ class CredibilityGraph(NamedTuple):
     total_reviews: torch.Tensor     # int32 [U]
     helpful_reviews: torch.Tensor   # int32 [U]
     stats: dict                     # E, ts_min, ts_max (None without timestamps), global_avg_len
+
+
+class CredibilityGraphV2(NamedTuple):
+    """``build_credibility_graph(.., feature_set="v2")``: the fields of
+    ``CredibilityGraph`` (``user_x`` in main_v2_.py's definitions, ``stats``
+    with ``global_avg_lenlog``), then ``user_extra``."""
+    src: torch.Tensor
+    dst: torch.Tensor
+    edge_attr: torch.Tensor
+    user_x: torch.Tensor
+    user_y: torch.Tensor
+    item_x: torch.Tensor
+    total_reviews: torch.Tensor
+    helpful_reviews: torch.Tensor
+    stats: dict
+    user_extra: torch.Tensor        # f32 [U, 2], USER_EXTRA_KEYS
 
 
 def _column(x, name: str, E: int, device, dtype) -> torch.Tensor:
@@ -165,7 +193,7 @@ def _with_workspace(fn: str, *args) -> None:
 
 
 def build_credibility_graph(cols: ReviewColumns, num_users: int, num_items: int,
-                            device="cuda") -> CredibilityGraph:
+                            device="cuda", feature_set: str = "main"):
     """Labels, user and item features and edge attributes of the records in
     `cols` (module docstring). Raises ValueError, before any launch, for an id
     outside [0, num_users) / [0, num_items) or E >= 2^31 - 1, and
@@ -175,12 +203,30 @@ def build_credibility_graph(cols: ReviewColumns, num_users: int, num_items: int,
     A user id with no record gets a NaN row of ``user_x`` and label -1; an
     item id with no record mean 0 and count 0. Without the two token columns
     they are counted from ``cols.text`` (``bbgr.text.token_counts``); ValueError
-    when neither is given or ``text`` has another number of records."""
+    when neither is given or ``text`` has another number of records.
+    ``feature_set="main"`` returns a ``CredibilityGraph``; ``"v2"`` (module
+    docstring) a ``CredibilityGraphV2`` and needs ``cols.text``: ValueError
+    naming text without it, or for text of 2^31 - 1 bytes or more; ``n_tokens``
+    is taken from the columns when given, else counted."""
     device = torch.device(device)
     if device.type != "cuda":
         raise ValueError("build_credibility_graph runs on the GPU; there is no CPU fallback")
+    if feature_set not in FEATURE_SETS:
+        raise ValueError(f"feature_set = {feature_set!r}: one of {FEATURE_SETS}")
     U, I, E = int(num_users), int(num_items), len(cols)
-    if cols.n_tokens is None or cols.n_unique_tokens is None:
+    v2 = feature_set == "v2"
+    if v2:
+        from .text import BYTES_MAX
+        if cols.text is None:
+            raise ValueError("feature_set='v2' needs cols.text: the pooled distinct-token count "
+                             "cannot be made from two integers per record")
+        if len(cols.text) != E:
+            raise ValueError(f"text: expected {E} records, got {len(cols.text)}")
+        span = int(cols.text.offsets[-1]) - int(cols.text.offsets[0])
+        if span >= BYTES_MAX:
+            raise ValueError(f"text of {span} bytes: feature_set='v2' takes the text as one "
+                             "chunk, which must be shorter than 2^31 - 1 bytes")
+    elif cols.n_tokens is None or cols.n_unique_tokens is None:
         if cols.text is None:
             raise ValueError("columns n_tokens / n_unique_tokens: give both, or text")
         if len(cols.text) != E:
@@ -193,12 +239,16 @@ def build_credibility_graph(cols: ReviewColumns, num_users: int, num_items: int,
         _check_ids(cols.user, "user", U, "num_users")
         _check_ids(cols.item, "item", I, "num_items")
     _lib.require_gpu()
-    if cols.n_tokens is None or cols.n_unique_tokens is None:
+    if v2 and cols.n_tokens is not None:
+        if cols.n_unique_tokens is None:     # not read by the v2 pass; the columns struct wants one
+            cols = dataclasses.replace(cols, n_unique_tokens=cols.n_tokens)
+    elif cols.n_tokens is None or cols.n_unique_tokens is None:
         from .text import token_counts
         n_tok, n_uniq, _ = token_counts(cols.text, device)
         cols = dataclasses.replace(cols, n_tokens=n_tok, n_unique_tokens=n_uniq)
     with torch.cuda.device(device):
-        return _Pipeline(cols, U, I, E, torch.device("cuda", torch.cuda.current_device())).run()
+        dev = torch.device("cuda", torch.cuda.current_device())
+        return (_PipelineV2 if v2 else _Pipeline)(cols, U, I, E, dev).run()
 
 
 class _Pipeline:
@@ -294,6 +344,64 @@ class _Pipeline:
                  "global_avg_len": self.global_avg_len}
         return CredibilityGraph(self.user, self.item, self.edge_attr, self.user_x, self.user_y,
                                 self.item_x, self.total, self.helpful_reviews, stats)
+
+
+class _PipelineV2(_Pipeline):
+    """The v2 build: `_Pipeline`'s launches with the v2 statistics beside
+    them, the pooled count and the gap entropy before the user pass, and
+    ``bbgr_feat_users_v2`` as the user pass."""
+
+    def __init__(self, cols: ReviewColumns, U: int, I: int, E: int, dev):
+        super().__init__(cols, U, I, E, dev)
+        self.text = cols.text
+        f64 = dict(dtype=torch.float64, device=dev)
+        self.lenlog_dev = torch.empty(1, **f64)
+        self.item_mean = torch.empty(max(I, 1), **f64)
+        self.etg = torch.empty(max(U, 1), **f64)
+        self.user_extra = torch.empty(U, len(USER_EXTRA_KEYS), dtype=torch.float32, device=dev)
+
+    def stats(self) -> None:
+        super().stats()
+        _with_workspace("bbgr_feat_lenlog", self.cref, ptr(self.lenlog_dev))
+
+    def read_stats(self) -> None:
+        """The one host read: four integers and the sum of log1p(n_tokens)."""
+        super().read_stats()
+        self.global_avg_lenlog = float(self.lenlog_dev) / max(self.E, 1)
+
+    def items(self) -> None:
+        super().items()
+        _with_workspace("bbgr_feat_item_means", self.cref, ptr(self.i_indptr), ptr(self.i_eid),
+                        ptr(self.item_mean))
+
+    def pooled(self) -> None:
+        from .text import pooled_token_counts
+        self.group_tokens, self.group_unique, self.pooled_info = pooled_token_counts(
+            self.text, self.user, self.U, self.dev)
+
+    def gaps(self) -> None:
+        _with_workspace("bbgr_feat_gaps", self.cref, ptr(self.u_indptr), ptr(self.u_eid),
+                        ptr(self.etg))
+
+    def users(self) -> None:
+        a = _lib.FeatUserV2Args()
+        a.u_indptr, a.u_eid = ptr(self.u_indptr), ptr(self.u_eid)
+        a.b_indptr, a.b_bucket = ptr(self.b_indptr), ptr(self.b_bucket)
+        a.item_mean, a.global_avg_lenlog = ptr(self.item_mean), self.global_avg_lenlog
+        a.group_tokens, a.group_unique = ptr(self.group_tokens), ptr(self.group_unique)
+        a.etg = ptr(self.etg)
+        a.user_x, a.user_y = ptr(self.user_x), ptr(self.user_y)
+        a.total_reviews, a.helpful_reviews = ptr(self.total), ptr(self.helpful_reviews)
+        a.user_extra = ptr(self.user_extra)
+        _with_workspace("bbgr_feat_users_v2", self.cref, ctypes.byref(a))
+
+    STEPS = ("stats", "read_stats", "buckets", "group_users", "group_items", "group_buckets",
+             "items", "pooled", "gaps", "users", "edges")
+
+    def run(self) -> CredibilityGraphV2:
+        g = super().run()
+        g.stats["global_avg_lenlog"] = self.global_avg_lenlog
+        return CredibilityGraphV2(*g, self.user_extra)
 
 
 # -- the host reader -------------------------------------------------------------------

@@ -24,6 +24,15 @@ the tokens' bytes on the device is what makes an unflagged record exact, not
 merely probable). Flagged records are counted again here on the host with
 ``features.tokenize``.
 
+``pooled_token_counts`` counts over all records of a group (the user) instead:
+``|set of all the group's tokens|`` and the group's token total, what
+main_v2_.py's pooled ``lexical_diversity`` divides. Equal tokens of different
+records must meet, so the text is resident as ONE chunk (below 2^31 - 1
+bytes; exact pooling across chunks would need a device-resident vocabulary and
+is not built). Flagged groups (one that owns a Kelvin record, or in which two
+different tokens share a hash) are counted again here on the host over the
+group's records.
+
 Launches per chunk: ``bbgr_text_count`` (one host read of the token total,
 which sizes the workspace), ``bbgr_text_unique``, one host read of the number
 of flagged records. Integer work only: two calls give the same bits.
@@ -212,3 +221,101 @@ def token_counts(text: ReviewText, device="cuda", chunk_bytes: int = 1 << 30, _h
         info = {"tokens": int(n_tok.sum(dtype=torch.int64)), "rechecked": flagged,
                 "chunks": len(chunks)}
         return n_tok, n_uniq, info
+
+
+def _check_groups(group, n: int, num_groups: int) -> None:
+    shape = tuple(group.shape)
+    if len(shape) != 1 or shape[0] != n:
+        raise ValueError(f"group: expected {n} entries, got shape {shape}")
+    if n == 0:
+        return
+    if isinstance(group, torch.Tensor):
+        lo, hi = (int(v) for v in torch.aminmax(group))
+    else:
+        lo, hi = int(np.min(group)), int(np.max(group))
+    if lo < 0 or hi >= num_groups:
+        raise ValueError(f"group id out of range: [{lo}, {hi}] not within "
+                         f"[0, num_groups = {num_groups})")
+
+
+def pooled_token_counts(text: ReviewText, group, num_groups: int, device="cuda",
+                        _hash_mask: int = 0, out=None):
+    """``(tokens, unique, info)`` per group: int64 [G] the sum of the token
+    counts of the group's records, int32 [G] the distinct tokens over all of
+    them (device tensors; a group without a record gets 0 and 0), and ``info =
+    {"tokens", "rechecked", "kelvin_records"}``: the token total, the groups
+    counted again on the host, the records that hold U+212A. ``group``: int32
+    [n], the group of each record (a host array or a tensor, also one on the
+    device). ``out``: optional ``(tokens, unique)`` device tensors to write.
+    ValueError before any launch for a group outside ``[0, num_groups)`` and
+    for text of 2^31 - 1 bytes or more: the text is one chunk (module
+    docstring). ``_hash_mask`` as for ``token_counts``."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise ValueError("pooled_token_counts runs on the GPU; there is no CPU fallback")
+    G = int(num_groups)
+    if G < 0 or G >= BYTES_MAX:
+        raise ValueError(f"num_groups = {G}: must lie in [0, 2^31 - 1)")
+    ends = (text.offsets.cpu().numpy() if isinstance(text.offsets, torch.Tensor)
+            else np.asarray(text.offsets))
+    if ends.ndim == 1 and ends.shape[0] > 1 and int(ends[-1]) - int(ends[0]) >= BYTES_MAX:
+        raise ValueError(f"text of {int(ends[-1]) - int(ends[0])} bytes: pooled counts take the "
+                         "text as one chunk, which must be shorter than 2^31 - 1 bytes")
+    data, off = _checked_text(text)
+    n = off.shape[0] - 1
+    if n >= BYTES_MAX:
+        raise ValueError(f"n = {n} records: n must be < 2^31 - 1")
+    if not isinstance(group, torch.Tensor):
+        group = np.asarray(group)
+    _check_groups(group, n, G)
+    _lib.require_gpu()
+    with torch.cuda.device(device):
+        dev = torch.device("cuda", torch.cuda.current_device())
+        grp = (group if isinstance(group, torch.Tensor) else torch.from_numpy(
+            np.ascontiguousarray(group))).to(device=dev, dtype=torch.int32).contiguous()
+        b0, b1 = int(off[0]), int(off[-1])
+        d = (_bytes_to(data[b0:b1], dev) if b1 > b0
+             else torch.zeros(1, dtype=torch.uint8, device=dev))
+        o = torch.from_numpy(off - b0).to(dev)
+        n_tok = torch.zeros(n, dtype=torch.int32, device=dev)
+        n_uniq = torch.zeros(n, dtype=torch.int32, device=dev)     # bbgr_text_args wants one
+        recheck = torch.zeros(n, dtype=torch.uint8, device=dev)
+        totals = torch.zeros(2, dtype=torch.int64, device=dev)
+        if out is None:
+            out = (torch.empty(G, dtype=torch.int64, device=dev),
+                   torch.empty(G, dtype=torch.int32, device=dev))
+        g_tok, g_uniq = out
+        if (g_tok.dtype, g_uniq.dtype) != (torch.int64, torch.int32) or \
+                not (g_tok.is_cuda and g_uniq.is_cuda and g_tok.is_contiguous()
+                     and g_uniq.is_contiguous()) or g_tok.numel() != G or g_uniq.numel() != G:
+            raise ValueError("out: (int64 [G], int32 [G]) contiguous device tensors")
+        g_flag = torch.empty(G, dtype=torch.uint8, device=dev)
+        a = _text_args(d, o, 0, b1 - b0, int(_hash_mask), n_tok, n_uniq, recheck, totals)
+        st = stream_handle()
+        call("bbgr_text_count", ctypes.byref(a), st)
+        tokens = int(totals[0])                                  # sizes the workspace
+        args = (ctypes.byref(a), tokens, ptr(grp), G, ptr(g_tok), ptr(g_uniq), ptr(g_flag))
+        nb = _lib.workspace_query("bbgr_text_unique_pooled", *args, args_after=(st,))
+        ws = torch.empty(max(nb, 1), dtype=torch.uint8, device=dev)
+        call("bbgr_text_unique_pooled", *args, ptr(ws), ctypes.byref(ctypes.c_size_t(nb)), st)
+        flagged = int(totals[1])
+        if flagged:
+            idx = torch.nonzero(g_flag).flatten()
+            g_host = grp.cpu().numpy()
+            order = np.argsort(g_host, kind="stable")
+            starts = np.searchsorted(g_host[order], np.arange(G + 1))
+            fixed = np.empty((idx.numel(), 2), np.int64)
+            for k, g in enumerate(idx.tolist()):
+                seen, total = set(), 0
+                for r in order[starts[g]:starts[g + 1]].tolist():
+                    toks = tokenize(_record_bytes(data, int(off[r]), int(off[r + 1]))
+                                    .decode("utf-8", "surrogatepass"))
+                    total += len(toks)
+                    seen.update(toks)
+                fixed[k] = (total, len(seen))
+            fixed_dev = torch.from_numpy(fixed).to(dev)
+            g_tok[idx] = fixed_dev[:, 0]
+            g_uniq[idx] = fixed_dev[:, 1].to(torch.int32)
+        info = {"tokens": int(g_tok.sum()), "rechecked": flagged,
+                "kelvin_records": int(recheck.sum(dtype=torch.int64))}
+        return g_tok, g_uniq, info

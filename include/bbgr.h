@@ -1445,6 +1445,103 @@ int bbgr_text_unique_stages(const bbgr_text_args *args, int64_t total_tokens, in
                             void *workspace, size_t *workspace_bytes, bbgr_stream_t stream);
 
 /* ------------------------------------------------------------------------- */
+/* The second feature pipeline (main_v2_.py:291-524): pooled lexical           */
+/* diversity, the entropy of temporal gaps (ETG), the share of low ratings     */
+/* (RNR), and the v2 forms of four behavioural columns. Appended; the ABI      */
+/* stays 12. Sums in double in a fixed order, no float atomics: two calls give */
+/* the same bits.                                                              */
+/* ------------------------------------------------------------------------- */
+/* Distinct normalised tokens over ALL records of a group, after               */
+/* bbgr_text_count on the same args (token rule, hash and hash_mask as above). */
+/* group [n]: the group of each record (here the user id); a record whose      */
+/* group lies outside [0, n_groups) is skipped (the caller checks them:        */
+/* bbgr.text does, before any launch).                                         */
+/*   group_tokens [n_groups] = the sum of n_tokens over the group's records    */
+/*   group_unique [n_groups] = its distinct tokens                             */
+/*   group_recheck [n_groups] = 1: the device does not vouch for this group:   */
+/*     it owns a record with recheck set, or two of its tokens with equal      */
+/*     hashes differ in their bytes                                            */
+/*   totals[1] = the number of flagged groups                                  */
+/* A group without a record gets 0 / 0 / 0. The token stream is                */
+/* bbgr_text_unique's EMIT stage (this call runs it, in the first part of the  */
+/* workspace); then a stable radix sort of all tokens by hash, one by group    */
+/* over the bits n_groups needs, and per sorted token: a new distinct token    */
+/* where the group or the hash differs from the left neighbour's, and with     */
+/* both equal a comparison of the two tokens' normalised bytes and lengths. An */
+/* unflagged group's count is therefore exact. total_tokens as for             */
+/* bbgr_text_unique; the text is one chunk (last - first < 2^31 - 1 bytes).    */
+/* The workspace holds 40 bytes per token, 4 per record and the sorts' own.    */
+/* Size query with workspace == NULL; stream-ordered, no synchronisation.      */
+int bbgr_text_unique_pooled(const bbgr_text_args *args, int64_t total_tokens,
+                            const int32_t *group, int32_t n_groups, int64_t *group_tokens,
+                            int32_t *group_unique, uint8_t *group_recheck, void *workspace,
+                            size_t *workspace_bytes, bbgr_stream_t stream);
+/* For measurement (tools/text_bench.py): its launch groups picked by `stages` */
+/* (BBGR_TEXT_STAGE_*): EMIT the token stream; SORT the two sorts and the      */
+/* group keys between them; VERIFY the memsets, the comparison, the per-record */
+/* pass and totals[1]. Out-of-range values read from a workspace no earlier    */
+/* group has filled are skipped, as in bbgr_text_unique_stages.                */
+int bbgr_text_unique_pooled_stages(const bbgr_text_args *args, int64_t total_tokens,
+                                   const int32_t *group, int32_t n_groups,
+                                   int64_t *group_tokens, int32_t *group_unique,
+                                   uint8_t *group_recheck, int32_t stages, void *workspace,
+                                   size_t *workspace_bytes, bbgr_stream_t stream);
+
+/* lenlog_sum (DEVICE double [1]) = the sum of log1p(n_tokens) over the        */
+/* records: 256 partial sums over a fixed grid, then one workgroup adds them.  */
+/* global_avg_lenlog is this / max(n, 1). Size query with workspace == NULL.   */
+int bbgr_feat_lenlog(const bbgr_feat_columns *c, double *lenlog_sum, void *workspace,
+                     size_t *workspace_bytes, bbgr_stream_t stream);
+
+/* item_mean [n_items] = the double mean of the raw rating over the            */
+/* reference-order item rows (bbgr_feat_items rounds the same sum to float);   */
+/* 0 for an item with no record. Size query with workspace == NULL.            */
+int bbgr_feat_item_means(const bbgr_feat_columns *c, const int32_t *i_indptr,
+                         const int32_t *i_eid, double *item_mean, void *workspace,
+                         size_t *workspace_bytes, bbgr_stream_t stream);
+
+/* etg [n_users] (double): per record with a timestamp days = (ts >= 10^12 ?   */
+/* double(ts) / 1000.0 : double(ts)) / 86400.0 (IEEE double divisions); per    */
+/* user over the reference-order user rows the days sorted (a segmented radix  */
+/* sort; +inf for a record without a timestamp), bin = min(floor(days[j + 1] - */
+/* days[j]), 365), and the natural-log entropy of the bins' histogram over the */
+/* non-empty bins in ascending order, p = count / gaps; 0 with fewer than 3    */
+/* timestamps. A row of at most 64 records is one lane's (it counts by value), */
+/* a longer one a workgroup's with the 366 counters in LDS. The workspace      */
+/* holds 16 bytes per record and the sort's own. Size query with workspace ==  */
+/* NULL.                                                                       */
+int bbgr_feat_gaps(const bbgr_feat_columns *c, const int32_t *u_indptr, const int32_t *u_eid,
+                   double *etg, void *workspace, size_t *workspace_bytes, bbgr_stream_t stream);
+
+/* bbgr_feat_users in main_v2_.py's definitions. total_reviews, helpful,       */
+/* Ru, user_y and user_x columns 0, 1, 2 as there;                             */
+/*   column 3 = mean |rating - item_mean[item]| (raw ratings)                  */
+/*   column 4 = ((records with a timestamp) - (distinct buckets)) / n          */
+/*   column 5 = group_unique / group_tokens, 0 when the user has no token      */
+/*   column 6 = mean |log1p(L) - global_avg_lenlog|                            */
+/*   user_extra [n_users, 2] = {RNR = #(ri <= 2) / n, ETG = etg[u]}            */
+/* A user with no record gets a NaN row in both tables, label -1 and zero      */
+/* counts. Row split, sums and workspace as for bbgr_feat_users.               */
+typedef struct {
+  const int32_t *u_indptr;      /* [n_users + 1] */
+  const int32_t *u_eid;         /* [n] */
+  const int32_t *b_indptr;      /* [n_users + 2] (row n_users: no timestamp) */
+  const int32_t *b_bucket;      /* [n] sorted within a row */
+  const double *item_mean;      /* [n_items] (bbgr_feat_item_means) */
+  double global_avg_lenlog;     /* bbgr_feat_lenlog's sum / max(n, 1) */
+  const int64_t *group_tokens;  /* [n_users] (bbgr_text_unique_pooled by user) */
+  const int32_t *group_unique;  /* [n_users] */
+  const double *etg;            /* [n_users] (bbgr_feat_gaps) */
+  float *user_x;                /* [n_users, 7] */
+  int64_t *user_y;              /* [n_users] */
+  int32_t *total_reviews;       /* [n_users] */
+  int32_t *helpful_reviews;     /* [n_users] */
+  float *user_extra;            /* [n_users, 2] */
+} bbgr_feat_user_v2_args;
+int bbgr_feat_users_v2(const bbgr_feat_columns *c, const bbgr_feat_user_v2_args *args,
+                       void *workspace, size_t *workspace_bytes, bbgr_stream_t stream);
+
+/* ------------------------------------------------------------------------- */
 /* Blueprint names (SURVEY §8(b)'s ABI sketch), thin forms of the above.      */
 /* ------------------------------------------------------------------------- */
 /* Y = diag(row_scale) A diag(col_scale) X (either scale NULL = ones), one    */

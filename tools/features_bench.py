@@ -1,6 +1,6 @@
 """Benchmark: review columns -> credibility graph tensors on MI355X.
 
-    python tools/features_bench.py [--config C2] [--reps 10] [--host]
+    python tools/features_bench.py [--config C2] [--reps 10] [--host] [--feature-set main|v2]
                                    [--out profiles/features/features_c2.json]
 
 Workload: synthetic review columns over the interaction graph of a config (C2:
@@ -16,6 +16,13 @@ counted at their payload, index arrays included) and the 8 TB/s of HBM:
   stats, buckets, edges          streaming passes over the records (csrc/features.hip)
   items, users                   one row per item / user, gathers by record id
   group_users / _items / _buckets  the three bbgr_csr_build (radix sort; time only)
+
+--feature-set v2 times the launches of the v2 build (main_v2_.py's features:
+the same groups plus lenlog and item means inside stats / items, and pooled,
+gaps and the v2 users pass) on the same columns with the 1M-review corpus of
+tools/text_bench.py as their text and its token counts as n_tokens; `pooled`
+is the whole bbgr.text.pooled_token_counts (its upload of the text and its
+host reads included). Default --out: profiles/features_v2/features_v2_c2.json.
 
 `build_ms` is one whole call from device-resident columns (host clock, one
 device read inside); `upload_ms` the host -> device copy of the columns.
@@ -107,18 +114,30 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--host", action="store_true", help="also time the host restatement")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--feature-set", default="main", choices=FT.FEATURE_SETS)
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("features_bench needs a GPU: no timing is taken without one")
-    out_path = args.out or os.path.join(ROOT, "profiles", "features",
-                                        f"features_{args.config.lower()}.json")
+    v2 = args.feature_set == "v2"
+    out_path = args.out or os.path.join(
+        ROOT, "profiles", "features_v2" if v2 else "features",
+        f"features{'_v2' if v2 else ''}_{args.config.lower()}.json")
     cfg = CONFIGS[args.config]
     U, I = cfg["num_users"], cfg["num_items"]
     t0 = time.perf_counter()
     cols = synthetic_columns(args.config)
     E = len(cols)
     log(f"columns drawn in {time.perf_counter() - t0:.1f} s: E = {E}")
-    rec = {"config": args.config, "users": U, "items": I, "records": E,
+    if v2:
+        if args.host:
+            raise SystemExit("--host times the main restatement only")
+        sys.path.insert(0, os.path.join(ROOT, "tools"))
+        from text_bench import synthetic_corpus
+        from bbgr import text as TX
+        cols.text = synthetic_corpus(E)
+        n_tok, n_uniq, _ = TX.token_counts(cols.text, "cuda")
+        cols.n_tokens, cols.n_unique_tokens = n_tok.cpu().numpy(), n_uniq.cpu().numpy()
+    rec = {"config": args.config, "feature_set": args.feature_set, "users": U, "items": I, "records": E,
            "max_user_degree": int(np.bincount(cols.user, minlength=U).max()),
            "max_item_degree": int(np.bincount(cols.item, minlength=I).max()),
            "device": torch.cuda.get_device_name(0), "hbm_peak_TBps": HBM_PEAK / 1e12}
@@ -126,11 +145,14 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     on_dev = FT.ReviewColumns(**{k: torch.from_numpy(np.ascontiguousarray(v)).to(dev)
-                                 for k, v in cols.__dict__.items()})
+                                 for k, v in cols.__dict__.items() if k != "text"})
     torch.cuda.synchronize()
     rec["upload_ms"] = (time.perf_counter() - t0) * 1e3
+    if v2:
+        on_dev.text = cols.text          # host bytes: the pooled call uploads them itself
+        rec["text_bytes"] = int(cols.text.data.shape[0])
 
-    p = FT._Pipeline(on_dev, U, I, E, dev)
+    p = (FT._PipelineV2 if v2 else FT._Pipeline)(on_dev, U, I, E, dev)
     p.stats()
     p.read_stats()
     moved = bytes_moved(E, U, I, p.n_ts)
@@ -139,7 +161,7 @@ def main():
         if step == "read_stats":
             continue
         r = timed_events(getattr(p, step), args.warmup, args.reps)
-        if step in moved:
+        if step in moved and not (v2 and step in ("stats", "items", "users")):
             r["bytes"] = moved[step]
             r["TBps"] = moved[step] / (r["median_ms"] * 1e-3) / 1e12
             r["of_hbm_peak"] = r["TBps"] * 1e12 / HBM_PEAK
@@ -149,7 +171,7 @@ def main():
     rec["kernels_sum_ms"] = sum(r["median_ms"] for r in kernels.values())
 
     def build():
-        return FT.build_credibility_graph(on_dev, U, I, dev)
+        return FT.build_credibility_graph(on_dev, U, I, dev, feature_set=args.feature_set)
 
     ts = []
     for k in range(args.warmup + args.reps):

@@ -154,6 +154,93 @@ def write_jsonl(path: str, strings: list, seed: int = 1) -> None:
                 "verified_purchase": bool(k & 1)}) + "\n")
 
 
+def pooled_main(args):
+    """--pooled: the launch groups of bbgr_text_unique_pooled on the same
+    corpus, its records assigned to the users of tools/features_bench.py's C2
+    columns (the same seeded draw); the whole pooled_token_counts from host
+    memory; and the host loop it replaces, a set per user over
+    features.tokenize (on --host-records records, scaled to all)."""
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    from features_bench import synthetic_columns
+    from bbgr.synthetic import CONFIGS
+    out_path = args.out or os.path.join(ROOT, "profiles", "features_v2", "text_pooled_c2.json")
+    U = CONFIGS["C2"]["num_users"]
+    user = np.ascontiguousarray(synthetic_columns("C2").user[:args.records])
+    text = synthetic_corpus(len(user))
+    n, nbytes = len(text), int(text.data.shape[0])
+    dev = torch.device("cuda", torch.cuda.current_device())
+    rec = {"records": n, "users": U, "text_bytes": nbytes,
+           "max_user_records": int(np.bincount(user, minlength=U).max()),
+           "device": torch.cuda.get_device_name(0)}
+    data, off = torch.from_numpy(text.data).to(dev), torch.from_numpy(text.offsets).to(dev)
+    grp = torch.from_numpy(user).to(dev)
+    n_tok = torch.zeros(n, dtype=torch.int32, device=dev)
+    n_uniq = torch.zeros(n, dtype=torch.int32, device=dev)
+    recheck = torch.zeros(n, dtype=torch.uint8, device=dev)
+    totals = torch.zeros(2, dtype=torch.int64, device=dev)
+    g_tok = torch.zeros(U, dtype=torch.int64, device=dev)
+    g_uniq = torch.zeros(U, dtype=torch.int32, device=dev)
+    g_flag = torch.zeros(U, dtype=torch.uint8, device=dev)
+    a = TX._text_args(data, off, 0, nbytes, 0, n_tok, n_uniq, recheck, totals)
+    st = _lib.stream_handle()
+    _lib.call("bbgr_text_count", ctypes.byref(a), st)
+    tokens = int(totals[0])
+    head = (ctypes.byref(a), tokens, _lib.ptr(grp), U, _lib.ptr(g_tok), _lib.ptr(g_uniq),
+            _lib.ptr(g_flag))
+    nb = _lib.workspace_query("bbgr_text_unique_pooled", *head, args_after=(st,))
+    ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+    rec.update(device_tokens=tokens, workspace_bytes=nb)
+
+    def stage(bits):
+        return lambda: _lib.call("bbgr_text_unique_pooled_stages", *head, bits, _lib.ptr(ws),
+                                 ctypes.byref(ctypes.c_size_t(nb)), st)
+
+    kernels = {name: timed_events(stage(bits), args.warmup, args.reps)
+               for name, bits in (("emit", 1), ("sort", 2), ("verify", 4))}
+    for name, r in kernels.items():
+        r["ns_per_token"] = r["median_ms"] * 1e6 / max(tokens, 1)
+        log(name, r)
+    rec["kernels"] = kernels
+    rec["kernels_sum_ms"] = sum(r["median_ms"] for r in kernels.values())
+    rec["flagged_groups"] = int(totals[1])
+    del ws
+    ts = []
+    for k in range(args.warmup + args.reps):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        d_tok, d_uniq, info = TX.pooled_token_counts(text, user, U, dev)
+        torch.cuda.synchronize()
+        if k >= args.warmup:
+            ts.append((time.perf_counter() - t0) * 1e3)
+    rec["call_ms"] = {"median_ms": statistics.median(ts), "min_ms": min(ts), "max_ms": max(ts),
+                      "reps": args.reps}
+    rec["info"] = info
+    log("call_ms", rec["call_ms"], info)
+    m = n if args.host_records is None else min(args.host_records, n)
+    strings = strings_of(text, m)
+    t0 = time.perf_counter()
+    sets, total = {}, np.zeros(U, np.int64)
+    for u, s in zip(user[:m].tolist(), strings):
+        toks = FT.tokenize(s)
+        total[u] += len(toks)
+        sets.setdefault(u, set()).update(toks)
+    host_s = time.perf_counter() - t0
+    rec["host_loop"] = {"records": m, "seconds": host_s, "us_per_record": host_s * 1e6 / max(m, 1)}
+    if m == n:
+        uniq = np.zeros(U, np.int32)
+        for u, v in sets.items():
+            uniq[u] = len(v)
+        rec["vs_host"] = {"tokens": bool(np.array_equal(d_tok.cpu().numpy(), total)),
+                          "unique": bool(np.array_equal(d_uniq.cpu().numpy(), uniq))}
+    rec["call_vs_host_loop"] = host_s * (n / max(m, 1)) * 1e3 / rec["call_ms"]["median_ms"]
+    log("host_loop", rec["host_loop"], rec.get("vs_host"))
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, "w") as f:
+        json.dump(rec, f, indent=1)
+        f.write("\n")
+    print(json.dumps(rec))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--records", type=int, default=1_000_000)
@@ -163,9 +250,13 @@ def main():
                     help="records of the host baseline (default: all)")
     ap.add_argument("--jsonl-lines", type=int, default=200_000)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--pooled", action="store_true",
+                    help="time bbgr.text.pooled_token_counts (distinct tokens per user) instead")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("text_bench needs a GPU: no timing is taken without one")
+    if args.pooled:
+        return pooled_main(args)
     out_path = args.out or os.path.join(ROOT, "profiles", "text", "text_c2.json")
     t0 = time.perf_counter()
     text = synthetic_corpus(args.records)
