@@ -66,6 +66,24 @@ inline bool ld_ok(const void *p, long ld, int d) {
 // Round a workspace carve offset up to 256 bytes.
 inline size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
 
+// The workspace protocol of an entry point `fn` that needs `need` bytes: a
+// null workspace asks for the size (*query, answered in *workspace_bytes), one
+// of fewer bytes is refused.
+inline int feat_workspace(const char *fn, size_t need, void *workspace, size_t *workspace_bytes,
+                          bool *query) {
+  BBGR_REQUIRE_IN(fn, workspace_bytes, "null workspace_bytes");
+  *query = workspace == nullptr;
+  if (!workspace) {
+    *workspace_bytes = need;
+    return BBGR_OK;
+  }
+  if (*workspace_bytes < need) {
+    set_error("%s: workspace %zu < %zu bytes", fn, *workspace_bytes, need);
+    return BBGR_ERR_WORKSPACE;
+  }
+  return BBGR_OK;
+}
+
 // ---------------------------------------------------------------------------
 // Philox4x32-10 (Salmon et al., SC'11). Counter (c0..c3), key (k0,k1).
 // ---------------------------------------------------------------------------

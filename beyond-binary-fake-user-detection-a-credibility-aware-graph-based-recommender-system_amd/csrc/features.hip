@@ -10,15 +10,12 @@
 // build over (user, day bucket) of the records that have a timestamp gives
 // each user's buckets sorted, so the distinct-bucket count is a boundary count.
 //
-// Every sum is taken in double in a fixed order and without float atomics:
-// a row of at most FEAT_LONG_ROW records is summed by one lane in file order
-// (the order of the reference's loops), a longer row by one workgroup: thread
-// t takes the records t, t + 256, ... in order, a xor tree adds the lanes of a
-// wave and the four waves are added in wave order. The shape depends on the
-// row's length alone, so two runs give the same bits. The long rows are handed
-// from the short-row kernel to the long-row kernel through a list filled with
-// an integer atomic counter; the list's order does not reach any result.
-// Results are rounded to float once, at the store.
+// The two row passes (ItemsPass, UsersPass) say only what a record adds and
+// what a row stores; features.h's row pass runs them: a row of at most
+// FEAT_LONG_ROW records is summed by one lane in file order (the order of the
+// reference's loops), a longer row by one workgroup in a fixed shape. Every
+// sum is taken in double, without float atomics, and rounded to float once, at
+// the store.
 //
 // Measured at 1M and 50M records in DESIGN 4d (tools/features_bench.py).
 #include "common.h"
@@ -115,186 +112,84 @@ __global__ __launch_bounds__(256) void feat_buckets_kernel(bbgr_feat_columns C, 
 // Per-item statistics: the count, the sum of the raw rating (item_x's mean)
 // and the sum of the rounded rating (the mean the user deviation is taken from)
 // ---------------------------------------------------------------------------
-struct ItemAcc {
-  double sum_r = 0.0;
-  long long sum_ri = 0;
+struct ItemsPass : SumPass<ItemsPass> {
+  bbgr_feat_columns C;
+  const int *eid;
+  float *item_x;
+  double *item_rbar;
+  struct Acc {
+    double sum_r = 0.0;
+    long long sum_ri = 0;
+    __device__ __forceinline__ void block_sum() {
+      __shared__ double s_d[4];
+      __shared__ long long s_l[4];
+      sum_r = feat_block_sum(sum_r, s_d);
+      sum_ri = feat_block_sum(sum_ri, s_l);
+    }
+  };
+  __device__ __forceinline__ void accumulate(int i, int start, int step, Acc &a) const {
+#pragma clang fp contract(off)
+    const int re = indptr[i + 1];
+#pragma unroll 4
+    for (int p = indptr[i] + start; p < re; p += step) {
+      const float r = C.rating[eid[p]];
+      a.sum_r += (double)r;
+      a.sum_ri += feat_ri(r);
+    }
+  }
+  __device__ __forceinline__ void store(int i, int n, const Acc &a) const {
+#pragma clang fp contract(off)
+    const double den = n > 0 ? (double)n : 1.0;
+    item_x[2L * i] = (float)(a.sum_r / den);
+    item_x[2L * i + 1] = (float)n;
+    item_rbar[i] = (double)a.sum_ri / den;
+  }
 };
 
-__device__ __forceinline__ void feat_item_acc(const bbgr_feat_columns &C, const int *eid, int rb,
-                                              int re, int start, int step, ItemAcc &a) {
+// ---------------------------------------------------------------------------
+// Per-user label and features: features.h's user pass with main.py's three
+// double sums and its columns 3 to 6
+// ---------------------------------------------------------------------------
+struct UsersPass : SumPass<UsersPass> {
+  bbgr_feat_columns C;
+  bbgr_feat_user_args A;
+  const int4 *packed;   // feat_pack_kernel<false>: z is n_unique_tokens
+  struct Acc : UserCounts {
+    double aad = 0.0, ld = 0.0, rd = 0.0;
+    __device__ __forceinline__ void block_sum() {
+      __shared__ double s_d[4];
+      UserCounts::block_sum();
+      aad = feat_block_sum(aad, s_d);
+      ld = feat_block_sum(ld, s_d);
+      rd = feat_block_sum(rd, s_d);
+    }
+  };
+  __device__ __forceinline__ void accumulate(int u, int start, int step, Acc &a) const {
 #pragma clang fp contract(off)
+    const int re = indptr[u + 1];
 #pragma unroll 4
-  for (int p = rb + start; p < re; p += step) {
-    const float r = C.rating[eid[p]];
-    a.sum_r += (double)r;
-    a.sum_ri += feat_ri(r);
+    for (int p = indptr[u] + start; p < re; p += step) {
+      const int4 r = packed[A.u_eid[p]];
+      a.add(r.w);
+      const double rbar = r.x >= 0 && r.x < C.n_items ? A.item_rbar[r.x] : (double)NAN;
+      a.aad += fabs((double)(r.w & 7) - rbar);
+      const int L = r.y;
+      if (L > 0) a.ld += (double)r.z / (double)L;
+      a.rd += fabs((double)L - A.global_avg_len);
+    }
+    a.add_buckets(A.b_indptr, A.b_bucket, u, start, step);
   }
-}
-
-__device__ __forceinline__ void feat_item_store(int i, int n, const ItemAcc &a, float *item_x,
-                                                double *item_rbar) {
-  const double den = n > 0 ? (double)n : 1.0;
-  item_x[2L * i] = (float)(a.sum_r / den);
-  item_x[2L * i + 1] = (float)n;
-  item_rbar[i] = (double)a.sum_ri / den;
-}
-
-__global__ __launch_bounds__(256) void feat_items_kernel(bbgr_feat_columns C, const int *indptr,
-                                                         const int *eid, float *item_x,
-                                                         double *item_rbar, int *long_count,
-                                                         int *long_rows, int long_cap) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= C.n_items) return;
-  const int rb = indptr[i], re = indptr[i + 1];
-  if (re - rb > FEAT_LONG_ROW) {
-    const int pos = atomicAdd(long_count, 1);
-    if (pos < long_cap) long_rows[pos] = i;   // always, for an indptr that ends at n
-    return;
+  __device__ __forceinline__ void store(int u, int n, const Acc &a) const {
+#pragma clang fp contract(off)
+    if (!feat_user_head(A, u, n, a)) return;
+    const double dn = (double)n;
+    float *x = A.user_x + 7L * u;
+    x[3] = (float)(a.aad / dn);
+    x[4] = (float)(a.n_ts - a.distinct);   // sum over the buckets of (count - 1)
+    x[5] = (float)(a.ld / dn);
+    x[6] = (float)(a.rd / dn);
   }
-  ItemAcc a;
-  feat_item_acc(C, eid, rb, re, 0, 1, a);
-  feat_item_store(i, re - rb, a, item_x, item_rbar);
-}
-
-__global__ __launch_bounds__(256) void feat_items_long_kernel(bbgr_feat_columns C,
-                                                              const int *indptr, const int *eid,
-                                                              float *item_x, double *item_rbar,
-                                                              const int *long_count,
-                                                              const int *long_rows, int long_cap) {
-  __shared__ double s_d[4];
-  __shared__ long long s_l[4];
-  const int n_long = min(*long_count, long_cap);
-  for (int j = blockIdx.x; j < n_long; j += gridDim.x) {
-    const int i = long_rows[j];
-    const int rb = indptr[i], re = indptr[i + 1];
-    ItemAcc a;
-    feat_item_acc(C, eid, rb, re, threadIdx.x, 256, a);
-    a.sum_r = feat_block_sum(a.sum_r, s_d);
-    a.sum_ri = feat_block_sum(a.sum_ri, s_l);
-    if (threadIdx.x == 0) feat_item_store(i, re - rb, a, item_x, item_rbar);
-  }
-}
-
-// ---------------------------------------------------------------------------
-// Per-user label and features
-// ---------------------------------------------------------------------------
-struct UserAcc {
-  int helpful = 0;
-  int h1 = 0, h2 = 0, h3 = 0, h4 = 0, h5 = 0;   // histogram of the rounded rating
-  int distinct = 0;                             // distinct day buckets
-  double aad = 0.0, ld = 0.0, rd = 0.0;
 };
-
-// What the user pass needs of a record, in one 16-byte word: gathered by
-// record id, five separate columns cost five memory lines per record, this one.
-// x: item, y: n_tokens, z: n_unique_tokens, w: ri | 8 when helpful_vote > 5.
-__global__ __launch_bounds__(256) void feat_pack_kernel(bbgr_feat_columns C, int4 *packed) {
-  const long e = (long)blockIdx.x * 256 + threadIdx.x;
-  if (e >= C.n) return;
-  packed[e] = make_int4(C.item[e], C.n_tokens[e], C.n_unique_tokens[e],
-                        feat_ri(C.rating[e]) | (C.helpful_vote[e] > 5 ? 8 : 0));
-}
-
-__device__ __forceinline__ void feat_user_acc(const bbgr_feat_columns &C,
-                                              const bbgr_feat_user_args &A, const int4 *packed,
-                                              int rb, int re, int bb, int be, int start, int step,
-                                              UserAcc &a) {
-#pragma clang fp contract(off)
-#pragma unroll 4
-  for (int p = rb + start; p < re; p += step) {
-    const int4 r = packed[A.u_eid[p]];
-    const int ri = r.w & 7;
-    a.h1 += ri == 1;
-    a.h2 += ri == 2;
-    a.h3 += ri == 3;
-    a.h4 += ri == 4;
-    a.h5 += ri == 5;
-    a.helpful += r.w >> 3;
-    const double rbar = r.x >= 0 && r.x < C.n_items ? A.item_rbar[r.x] : (double)NAN;
-    a.aad += fabs((double)ri - rbar);
-    const int L = r.y;
-    if (L > 0) a.ld += (double)r.z / (double)L;
-    a.rd += fabs((double)L - A.global_avg_len);
-  }
-  for (int p = bb + start; p < be; p += step)
-    a.distinct += (p == bb || A.b_bucket[p] != A.b_bucket[p - 1]) ? 1 : 0;
-}
-
-__device__ __forceinline__ void feat_user_store(const bbgr_feat_user_args &A, int u, int n,
-                                                int n_ts, const UserAcc &a) {
-#pragma clang fp contract(off)
-  float *x = A.user_x + 7L * u;
-  A.total_reviews[u] = n;
-  A.helpful_reviews[u] = a.helpful;
-  if (n == 0) {   // no record: the NaN row of the graph pass, unlabeled
-#pragma unroll
-    for (int f = 0; f < 7; ++f) x[f] = NAN;
-    A.user_y[u] = -1;
-    return;
-  }
-  const double dn = (double)n;
-  const double Ru = (double)a.helpful / dn;
-  A.user_y[u] = Ru >= 0.7 ? 1 : (Ru <= 0.3 ? 0 : -1);
-  double H = 0.0;
-  H = feat_plogp(H, a.h1, dn);
-  H = feat_plogp(H, a.h2, dn);
-  H = feat_plogp(H, a.h3, dn);
-  H = feat_plogp(H, a.h4, dn);
-  H = feat_plogp(H, a.h5, dn);
-  x[0] = (float)Ru;
-  x[1] = (float)H;
-  x[2] = (float)((double)(a.h1 + a.h5) / dn);
-  x[3] = (float)(a.aad / dn);
-  x[4] = (float)(n_ts - a.distinct);   // sum over the buckets of (count - 1)
-  x[5] = (float)(a.ld / dn);
-  x[6] = (float)(a.rd / dn);
-}
-
-__global__ __launch_bounds__(256) void feat_users_kernel(bbgr_feat_columns C, bbgr_feat_user_args A,
-                                                         const int4 *packed, int *long_count,
-                                                         int *long_rows,
-                                                         int long_cap) {
-  const int u = blockIdx.x * 256 + threadIdx.x;
-  if (u >= C.n_users) return;
-  const int rb = A.u_indptr[u], re = A.u_indptr[u + 1];
-  if (re - rb > FEAT_LONG_ROW) {
-    const int pos = atomicAdd(long_count, 1);
-    if (pos < long_cap) long_rows[pos] = u;   // always, for an indptr that ends at n
-    return;
-  }
-  const int bb = A.b_indptr[u], be = A.b_indptr[u + 1];
-  UserAcc a;
-  feat_user_acc(C, A, packed, rb, re, bb, be, 0, 1, a);
-  feat_user_store(A, u, re - rb, be - bb, a);
-}
-
-__global__ __launch_bounds__(256) void feat_users_long_kernel(bbgr_feat_columns C,
-                                                              bbgr_feat_user_args A,
-                                                              const int4 *packed,
-                                                              const int *long_count,
-                                                              const int *long_rows, int long_cap) {
-  __shared__ double s_d[4];
-  __shared__ int s_i[4];
-  const int n_long = min(*long_count, long_cap);
-  for (int j = blockIdx.x; j < n_long; j += gridDim.x) {
-    const int u = long_rows[j];
-    const int rb = A.u_indptr[u], re = A.u_indptr[u + 1];
-    const int bb = A.b_indptr[u], be = A.b_indptr[u + 1];
-    UserAcc a;
-    feat_user_acc(C, A, packed, rb, re, bb, be, threadIdx.x, 256, a);
-    a.helpful = feat_block_sum(a.helpful, s_i);
-    a.h1 = feat_block_sum(a.h1, s_i);
-    a.h2 = feat_block_sum(a.h2, s_i);
-    a.h3 = feat_block_sum(a.h3, s_i);
-    a.h4 = feat_block_sum(a.h4, s_i);
-    a.h5 = feat_block_sum(a.h5, s_i);
-    a.distinct = feat_block_sum(a.distinct, s_i);
-    a.aad = feat_block_sum(a.aad, s_d);
-    a.ld = feat_block_sum(a.ld, s_d);
-    a.rd = feat_block_sum(a.rd, s_d);
-    if (threadIdx.x == 0) feat_user_store(A, u, re - rb, be - bb, a);
-  }
-}
 
 // ---------------------------------------------------------------------------
 // Per-edge attributes, EDGE_ATTR_KEYS order: verified, rating_align, rating,
@@ -388,45 +283,32 @@ extern "C" int bbgr_feat_buckets(const bbgr_feat_columns *c, int64_t ts_min, int
 extern "C" int bbgr_feat_items(const bbgr_feat_columns *c, const int32_t *i_indptr,
                                const int32_t *i_eid, float *item_x, double *item_rbar,
                                void *workspace, size_t *workspace_bytes, bbgr_stream_t stream) {
-  int rc = feat_columns_ok("bbgr_feat_items", c);
+  static const char *fn = "bbgr_feat_items";
+  int rc = feat_columns_ok(fn, c);
   if (rc) return rc;
-  BBGR_REQUIRE(workspace_bytes, "bbgr_feat_items: null workspace_bytes");
   bool query;
-  rc = feat_workspace("bbgr_feat_items", feat_long_bytes((long)c->n), workspace, workspace_bytes,
-                      &query);
+  rc = feat_workspace(fn, feat_long_bytes((long)c->n), workspace, workspace_bytes, &query);
   if (rc || query) return rc;
   if (c->n_items == 0) return BBGR_OK;
   BBGR_REQUIRE(i_indptr, "bbgr_feat_items: null i_indptr");
   BBGR_REQUIRE(c->n == 0 || i_eid, "bbgr_feat_items: null i_eid");
   BBGR_REQUIRE(item_x, "bbgr_feat_items: null item_x");
   BBGR_REQUIRE(item_rbar, "bbgr_feat_items: null item_rbar");
-  hipStream_t st = as_stream(stream);
-  int *long_count = static_cast<int *>(workspace);
-  int *long_rows = reinterpret_cast<int *>(static_cast<char *>(workspace) + 256);
-  const int long_cap = (int)(c->n / FEAT_LONG_ROW + 1);
-  BBGR_HIP(hipMemsetAsync(long_count, 0, sizeof(int), st));
-  hipLaunchKernelGGL(feat_items_kernel, dim3((unsigned)((c->n_items + 255) / 256)), dim3(256), 0,
-                     st, *c, i_indptr, i_eid, item_x, item_rbar, long_count, long_rows, long_cap);
-  BBGR_LAUNCHED("feat_items_kernel");
-  if (c->n > FEAT_LONG_ROW) {
-    hipLaunchKernelGGL(feat_items_long_kernel, dim3(FEAT_LONG_GRID), dim3(256), 0, st, *c,
-                       i_indptr, i_eid, item_x, item_rbar, long_count, long_rows, long_cap);
-    BBGR_LAUNCHED("feat_items_long_kernel");
-  }
-  return BBGR_OK;
+  return feat_row_pass(fn, ItemsPass{{i_indptr}, *c, i_eid, item_x, item_rbar}, c->n_items,
+                       (long)c->n, workspace, as_stream(stream));
 }
 
 extern "C" int bbgr_feat_users(const bbgr_feat_columns *c, const bbgr_feat_user_args *a,
                                void *workspace, size_t *workspace_bytes, bbgr_stream_t stream) {
-  int rc = feat_columns_ok("bbgr_feat_users", c);
+  static const char *fn = "bbgr_feat_users";
+  int rc = feat_columns_ok(fn, c);
   if (rc) return rc;
   BBGR_REQUIRE(a, "bbgr_feat_users: null args");
-  BBGR_REQUIRE(workspace_bytes, "bbgr_feat_users: null workspace_bytes");
   bool query;
   // the long-row list, then the packed records
   const size_t off_packed = feat_long_bytes((long)c->n);
-  rc = feat_workspace("bbgr_feat_users", off_packed + align_up(sizeof(int4) * (size_t)c->n),
-                      workspace, workspace_bytes, &query);
+  rc = feat_workspace(fn, off_packed + align_up(sizeof(int4) * (size_t)c->n), workspace,
+                      workspace_bytes, &query);
   if (rc || query) return rc;
   if (c->n_users == 0) return BBGR_OK;
   BBGR_REQUIRE(a->u_indptr, "bbgr_feat_users: null u_indptr");
@@ -441,25 +323,10 @@ extern "C" int bbgr_feat_users(const bbgr_feat_columns *c, const bbgr_feat_user_
   BBGR_REQUIRE(a->total_reviews, "bbgr_feat_users: null total_reviews");
   BBGR_REQUIRE(a->helpful_reviews, "bbgr_feat_users: null helpful_reviews");
   hipStream_t st = as_stream(stream);
-  int *long_count = static_cast<int *>(workspace);
-  int *long_rows = reinterpret_cast<int *>(static_cast<char *>(workspace) + 256);
-  const int long_cap = (int)(c->n / FEAT_LONG_ROW + 1);
-  BBGR_HIP(hipMemsetAsync(long_count, 0, sizeof(int), st));
   int4 *packed = reinterpret_cast<int4 *>(static_cast<char *>(workspace) + off_packed);
-  if (c->n > 0) {
-    hipLaunchKernelGGL(feat_pack_kernel, dim3((unsigned)((c->n + 255) / 256)), dim3(256), 0, st,
-                       *c, packed);
-    BBGR_LAUNCHED("feat_pack_kernel");
-  }
-  hipLaunchKernelGGL(feat_users_kernel, dim3((unsigned)((c->n_users + 255) / 256)), dim3(256), 0,
-                     st, *c, *a, packed, long_count, long_rows, long_cap);
-  BBGR_LAUNCHED("feat_users_kernel");
-  if (c->n > FEAT_LONG_ROW) {
-    hipLaunchKernelGGL(feat_users_long_kernel, dim3(FEAT_LONG_GRID), dim3(256), 0, st, *c, *a,
-                       packed, long_count, long_rows, long_cap);
-    BBGR_LAUNCHED("feat_users_long_kernel");
-  }
-  return BBGR_OK;
+  if ((rc = feat_pack<false>(c, packed, st))) return rc;
+  return feat_row_pass(fn, UsersPass{{a->u_indptr}, *c, *a, packed}, c->n_users, (long)c->n,
+                       workspace, st);
 }
 
 extern "C" int bbgr_feat_edges(const bbgr_feat_columns *c, const float *item_x, int64_t ts_min,

@@ -9,25 +9,28 @@
 // hash (text.hip; the same rule, the same hash, the same mask). Two stable
 // radix sorts bring equal (group, hash) pairs side by side: all tokens by
 // hash, then by group over the bits n_groups needs (the hash order survives
-// inside a group). pool_verify_kernel, one lane per sorted slot, is
-// text_verify_kernel's rule with the group in the record's place: a slot opens
-// a distinct token when its group or its hash differs from its left
-// neighbour's; with both equal the two tokens' normalised bytes are compared
-// to their ends and any difference flags the group. A group that owns a record
-// bbgr_text_count flagged (U+212A) is flagged too. Integer work only.
+// inside a group). pool_verify_kernel, one lane per sorted slot, applies
+// text_verify_kernel's rule (text.h: the comparison, the count per wave) with
+// the group in the record's place: a slot opens a distinct token when its
+// group or its hash differs from its left neighbour's; with both equal the two
+// tokens' normalised bytes are compared to their ends and any difference flags
+// the group. A group that owns a record bbgr_text_count flagged (U+212A) is
+// flagged too. Integer work only.
 //
 // bbgr_feat_gaps: days = (ts >= 10^12 ? double(ts) / 1000.0 : double(ts)) /
 // 86400.0 per record in the user rows' order (+inf without a timestamp),
 // hipcub's segmented radix sort inside each user row, then per user the
 // histogram of min(floor(days[j + 1] - days[j]), 365) and its entropy over the
-// non-empty bins in ascending order. A row of at most GAP_SHORT_ROW records is
-// one lane's: it counts by value (for each distinct bin in ascending order one
+// non-empty bins in ascending order. GapsPass runs through features.h's row
+// pass with its own limit: a row of at most GAP_SHORT_ROW records is one
+// lane's, which counts by value (for each distinct bin in ascending order one
 // scan of the row), since 366 counters do not fit a lane's registers; a longer
 // row is one workgroup's with the histogram in LDS (integer atomics), thread t
 // taking bins t and t + 256 and the fixed-shape workgroup sum adding them.
 //
-// bbgr_feat_users_v2 follows bbgr_feat_users: the same row split at
-// FEAT_LONG_ROW, the same fixed-shape double sums, one rounding at the store.
+// ItemMeansPass and UsersV2Pass are sum passes of features.h like
+// features.hip's two; the user pass shares its counts, its label and columns
+// 0 to 2 with bbgr_feat_users' and adds its own two double sums and columns.
 // No fast-math flag on this file: the divisions above must be IEEE double.
 //
 // Measured in DESIGN 4g (tools/features_bench.py, tools/text_bench.py).
@@ -43,20 +46,6 @@ constexpr int GAP_BINS = 366;        // whole days 0 .. 365, the last one the ca
 constexpr int GAP_SHORT_ROW = 64;    // records; above: one workgroup and an LDS histogram
 constexpr int LENLOG_GRID = 256;     // partial sums of log1p(n_tokens): a fixed grid, a fixed order
 
-// Row bounds of a segmented sort from an indptr: both clamped into [0, n] and
-// end >= begin, so no indptr, however wrong, sends the sort outside its keys.
-struct RowBound {
-  const int *indptr;
-  int n;
-  bool end;
-  __host__ __device__ __forceinline__ int clamp(int v) const { return v < 0 ? 0 : (v < n ? v : n); }
-  __host__ __device__ __forceinline__ int operator()(int r) const {
-    const int b = clamp(indptr[r]);
-    if (!end) return b;
-    const int e = clamp(indptr[r + 1]);
-    return e < b ? b : e;
-  }
-};
 typedef hipcub::TransformInputIterator<int, RowBound, hipcub::CountingInputIterator<int>> RowIter;
 
 // ---------------------------------------------------------------------------
@@ -92,7 +81,6 @@ __global__ __launch_bounds__(256) void pool_verify_kernel(TextTokens T,
                                                           int *group_unique,
                                                           uint8_t *group_recheck) {
   const long j = (long)blockIdx.x * 256 + threadIdx.x;
-  const int lane = threadIdx.x & 63;
   const long live_tokens = text_live_tokens(T);
   int g = -1;
   long t = 0;
@@ -107,26 +95,10 @@ __global__ __launch_bounds__(256) void pool_verify_kernel(TextTokens T,
     const long tl = (long)vals[j - 1];
     if (gkey[j - 1] == (uint32_t)g && tl < live_tokens && hash[tl] == hash[t]) {
       opens = false;
-      TokenCursor a = text_cursor(T, t), b = text_cursor(T, tl);
-      for (;;) {
-        const int x = a.next(), y = b.next();
-        if (x != y) {
-          group_recheck[g] = 1;   // every writer stores the same value
-          break;
-        }
-        if (x < 0) break;
-      }
+      if (text_tokens_differ(T, t, tl)) group_recheck[g] = 1;   // every writer stores the same value
     }
   }
-  const int left = __shfl_up(g, 1);
-  const unsigned long long heads = __ballot(lane == 0 || g != left), open_m = __ballot(opens);
-  if (live && (heads >> lane & 1ull)) {
-    const unsigned long long after = lane == 63 ? 0ull : heads >> (lane + 1);
-    const int len = after ? __ffsll((long long)after) : 64 - lane;   // lanes of this group here
-    const unsigned long long mine = (len == 64 ? ~0ull : (1ull << len) - 1ull) << lane;
-    const int cnt = __popcll(open_m & mine);
-    if (cnt) atomicAdd(group_unique + g, cnt);
-  }
+  text_count_opens(g, live, opens, group_unique);
 }
 
 // Per record: its tokens to its group's total, its U+212A flag to its group.
@@ -142,17 +114,6 @@ __global__ __launch_bounds__(256) void pool_records_kernel(long n, const int *n_
   const int L = n_tokens[r];
   if (L > 0) atomicAdd(group_tokens + g, (unsigned long long)L);
   if (recheck[r]) group_recheck[g] = 1;
-}
-
-__global__ __launch_bounds__(256) void pool_flagged_kernel(int n_groups, const uint8_t *flag,
-                                                           long long *totals) {
-  long cnt = 0;
-  for (long g = (long)blockIdx.x * 256 + threadIdx.x; g < n_groups; g += (long)gridDim.x * 256)
-    cnt += flag[g] != 0;
-#pragma unroll
-  for (int o = 32; o; o >>= 1) cnt += __shfl_xor(cnt, o);
-  if ((threadIdx.x & 63) == 0 && cnt)
-    atomicAdd(reinterpret_cast<unsigned long long *>(totals) + 1, (unsigned long long)cnt);
 }
 
 // ---------------------------------------------------------------------------
@@ -182,47 +143,29 @@ __global__ __launch_bounds__(256) void feat2_lenlog_final_kernel(const double *p
 // Per item the double mean of the raw rating (item_sum[item] += r_ui in file
 // order for a short row; 0 for an item with no record)
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ double feat2_item_sum(const bbgr_feat_columns &C, const int *eid, int rb,
-                                                 int re, int start, int step) {
+struct ItemMeansPass : SumPass<ItemMeansPass> {
+  bbgr_feat_columns C;
+  const int *eid;
+  double *item_mean;
+  struct Acc {
+    double s = 0.0;
+    __device__ __forceinline__ void block_sum() {
+      __shared__ double s_d[4];
+      s = feat_block_sum(s, s_d);
+    }
+  };
+  __device__ __forceinline__ void accumulate(int i, int start, int step, Acc &a) const {
 #pragma clang fp contract(off)
-  double s = 0.0;
+    const int re = indptr[i + 1];
 #pragma unroll 4
-  for (int p = rb + start; p < re; p += step) s += (double)C.rating[eid[p]];
-  return s;
-}
-
-__global__ __launch_bounds__(256) void feat2_item_means_kernel(bbgr_feat_columns C,
-                                                               const int *indptr, const int *eid,
-                                                               double *item_mean, int *long_count,
-                                                               int *long_rows, int long_cap) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= C.n_items) return;
-  const int rb = indptr[i], re = indptr[i + 1];
-  if (re - rb > FEAT_LONG_ROW) {
-    const int pos = atomicAdd(long_count, 1);
-    if (pos < long_cap) long_rows[pos] = i;   // always, for an indptr that ends at n
-    return;
+    for (int p = indptr[i] + start; p < re; p += step) a.s += (double)C.rating[eid[p]];
   }
-  const double s = feat2_item_sum(C, eid, rb, re, 0, 1);
-  item_mean[i] = re > rb ? s / (double)(re - rb) : 0.0;
-}
-
-__global__ __launch_bounds__(256) void feat2_item_means_long_kernel(bbgr_feat_columns C,
-                                                                    const int *indptr,
-                                                                    const int *eid,
-                                                                    double *item_mean,
-                                                                    const int *long_count,
-                                                                    const int *long_rows,
-                                                                    int long_cap) {
-  __shared__ double s_d[4];
-  const int n_long = min(*long_count, long_cap);
-  for (int j = blockIdx.x; j < n_long; j += gridDim.x) {
-    const int i = long_rows[j];
-    const int rb = indptr[i], re = indptr[i + 1];
-    const double s = feat_block_sum(feat2_item_sum(C, eid, rb, re, threadIdx.x, 256), s_d);
-    if (threadIdx.x == 0) item_mean[i] = s / (double)(re - rb);
+  // n > 0 in a long row, which therefore divides as it always did
+  __device__ __forceinline__ void store(int i, int n, const Acc &a) const {
+#pragma clang fp contract(off)
+    item_mean[i] = n > 0 ? a.s / (double)n : 0.0;
   }
-}
+};
 
 // ---------------------------------------------------------------------------
 // Gap entropy
@@ -251,50 +194,44 @@ __device__ __forceinline__ int feat2_gap_bin(const double *days, int p) {
   return (int)fmin(floor(gap), (double)(GAP_BINS - 1));
 }
 
-__global__ __launch_bounds__(256) void feat2_gaps_kernel(int n_users, RowBound rb_of, RowBound re_of,
-                                                         const double *days, double *etg,
-                                                         int *long_count, int *long_rows,
-                                                         int long_cap) {
-  const int u = blockIdx.x * 256 + threadIdx.x;
-  if (u >= n_users) return;
-  const int rb = rb_of(u), re = re_of(u);
-  if (re - rb > GAP_SHORT_ROW) {
-    const int pos = atomicAdd(long_count, 1);
-    if (pos < long_cap) long_rows[pos] = u;   // always: fewer than n / GAP_SHORT_ROW such rows
-    return;
-  }
-  int m = 0;   // the finite days are the row's first m: +inf sorts last
-  while (rb + m < re && days[rb + m] < (double)INFINITY) ++m;
-  double H = 0.0;
-  if (m >= 3) {
-    const int gaps = m - 1;
-    for (int cur = -1;;) {   // the distinct bins in ascending order, one scan each
-      int next = INT_MAX, cnt = 0;
-      for (int j = 0; j < gaps; ++j) {
-        const int b = feat2_gap_bin(days, rb + j);
-        if (b > cur && b <= next) {
-          cnt = b < next ? 1 : cnt + 1;
-          next = b;
+// A row pass of its own shape: the rows are the sorted days of a user, by the
+// clamped bounds the sort used.
+struct GapsPass {
+  static constexpr int LONG_ROW = GAP_SHORT_ROW;
+  const int *indptr;
+  int n;
+  const double *days;
+  double *etg;
+  __device__ __forceinline__ int rb_of(int u) const { return RowBound{indptr, n, false}(u); }
+  __device__ __forceinline__ int re_of(int u) const { return RowBound{indptr, n, true}(u); }
+  __device__ __forceinline__ int length(int u) const { return re_of(u) - rb_of(u); }
+  __device__ __forceinline__ void short_row(int u) const {
+    const int rb = rb_of(u), re = re_of(u);
+    int m = 0;   // the finite days are the row's first m: +inf sorts last
+    while (rb + m < re && days[rb + m] < (double)INFINITY) ++m;
+    double H = 0.0;
+    if (m >= 3) {
+      const int gaps = m - 1;
+      for (int cur = -1;;) {   // the distinct bins in ascending order, one scan each
+        int next = INT_MAX, cnt = 0;
+        for (int j = 0; j < gaps; ++j) {
+          const int b = feat2_gap_bin(days, rb + j);
+          if (b > cur && b <= next) {
+            cnt = b < next ? 1 : cnt + 1;
+            next = b;
+          }
         }
+        if (next == INT_MAX) break;
+        H = feat_plogp(H, cnt, (double)gaps);
+        cur = next;
       }
-      if (next == INT_MAX) break;
-      H = feat_plogp(H, cnt, (double)gaps);
-      cur = next;
     }
+    etg[u] = H;
   }
-  etg[u] = H;
-}
-
-__global__ __launch_bounds__(256) void feat2_gaps_long_kernel(RowBound rb_of, RowBound re_of,
-                                                              const double *days, double *etg,
-                                                              const int *long_count,
-                                                              const int *long_rows, int long_cap) {
-  __shared__ int s_hist[GAP_BINS];
-  __shared__ double s_d[4];
-  __shared__ int s_i[4];
-  const int n_long = min(*long_count, long_cap);
-  for (int j = blockIdx.x; j < n_long; j += gridDim.x) {
-    const int u = long_rows[j];
+  __device__ __forceinline__ void long_row(int u) const {
+    __shared__ int s_hist[GAP_BINS];
+    __shared__ double s_d[4];
+    __shared__ int s_i[4];
     const int rb = rb_of(u), re = re_of(u);
     for (int b = threadIdx.x; b < GAP_BINS; b += 256) s_hist[b] = 0;
     int fin = 0;
@@ -307,146 +244,64 @@ __global__ __launch_bounds__(256) void feat2_gaps_long_kernel(RowBound rb_of, Ro
     double h = 0.0;
     if (m >= 3)
       for (int b = threadIdx.x; b < GAP_BINS; b += 256) h = feat_plogp(h, s_hist[b], (double)gaps);
-    h = feat_block_sum(h, s_d);
+    h = feat_block_sum(h, s_d);   // and its last barrier frees the histogram for the next row
     if (threadIdx.x == 0) etg[u] = h;
   }
-}
-
-// ---------------------------------------------------------------------------
-// Per-user label and the v2 features
-// ---------------------------------------------------------------------------
-struct UserAcc2 {
-  int helpful = 0;
-  int h1 = 0, h2 = 0, h3 = 0, h4 = 0, h5 = 0;   // histogram of the rounded rating
-  int distinct = 0;                             // distinct day buckets
-  double ard = 0.0, rd = 0.0;
 };
 
-// What the pass needs of a record, in one 16-byte word. x: item, y: n_tokens,
-// z: the raw rating's bits, w: ri | 8 when helpful_vote > 5.
-__global__ __launch_bounds__(256) void feat2_pack_kernel(bbgr_feat_columns C, int4 *packed) {
-  const long e = (long)blockIdx.x * 256 + threadIdx.x;
-  if (e >= C.n) return;
-  const float r = C.rating[e];
-  packed[e] = make_int4(C.item[e], C.n_tokens[e], __float_as_int(r),
-                        feat_ri(r) | (C.helpful_vote[e] > 5 ? 8 : 0));
-}
-
-__device__ __forceinline__ void feat2_user_acc(const bbgr_feat_columns &C,
-                                               const bbgr_feat_user_v2_args &A,
-                                               const int4 *packed, int rb, int re, int bb, int be,
-                                               int start, int step, UserAcc2 &a) {
+// ---------------------------------------------------------------------------
+// Per-user label and the v2 features: features.h's user pass with
+// main_v2_.py's two double sums, its columns 3 to 6 and user_extra
+// ---------------------------------------------------------------------------
+struct UsersV2Pass : SumPass<UsersV2Pass> {
+  bbgr_feat_columns C;
+  bbgr_feat_user_v2_args A;
+  const int4 *packed;   // feat_pack_kernel<true>: z is the raw rating's bits
+  struct Acc : UserCounts {
+    double ard = 0.0, rd = 0.0;
+    __device__ __forceinline__ void block_sum() {
+      __shared__ double s_d[4];
+      UserCounts::block_sum();
+      ard = feat_block_sum(ard, s_d);
+      rd = feat_block_sum(rd, s_d);
+    }
+  };
+  __device__ __forceinline__ void accumulate(int u, int start, int step, Acc &a) const {
 #pragma clang fp contract(off)
+    const int re = indptr[u + 1];
 #pragma unroll 2
-  for (int p = rb + start; p < re; p += step) {
-    const int4 r = packed[A.u_eid[p]];
-    const int ri = r.w & 7;
-    a.h1 += ri == 1;
-    a.h2 += ri == 2;
-    a.h3 += ri == 3;
-    a.h4 += ri == 4;
-    a.h5 += ri == 5;
-    a.helpful += r.w >> 3;
-    const double mean = r.x >= 0 && r.x < C.n_items ? A.item_mean[r.x] : (double)NAN;
-    a.ard += fabs((double)__int_as_float(r.z) - mean);
-    a.rd += fabs(log1p((double)r.y) - A.global_avg_lenlog);
+    for (int p = indptr[u] + start; p < re; p += step) {
+      const int4 r = packed[A.u_eid[p]];
+      a.add(r.w);
+      const double mean = r.x >= 0 && r.x < C.n_items ? A.item_mean[r.x] : (double)NAN;
+      a.ard += fabs((double)__int_as_float(r.z) - mean);
+      a.rd += fabs(log1p((double)r.y) - A.global_avg_lenlog);
+    }
+    a.add_buckets(A.b_indptr, A.b_bucket, u, start, step);
   }
-  for (int p = bb + start; p < be; p += step)
-    a.distinct += (p == bb || A.b_bucket[p] != A.b_bucket[p - 1]) ? 1 : 0;
-}
-
-__device__ __forceinline__ void feat2_user_store(const bbgr_feat_user_v2_args &A, int u, int n,
-                                                 int n_ts, const UserAcc2 &a) {
+  __device__ __forceinline__ void store(int u, int n, const Acc &a) const {
 #pragma clang fp contract(off)
-  float *x = A.user_x + 7L * u;
-  float *extra = A.user_extra + 2L * u;
-  A.total_reviews[u] = n;
-  A.helpful_reviews[u] = a.helpful;
-  if (n == 0) {   // no record: the NaN row of the graph pass, unlabeled
-#pragma unroll
-    for (int f = 0; f < 7; ++f) x[f] = NAN;
-    extra[0] = NAN;
-    extra[1] = NAN;
-    A.user_y[u] = -1;
-    return;
+    float *x = A.user_x + 7L * u;
+    float *extra = A.user_extra + 2L * u;
+    if (!feat_user_head(A, u, n, a)) {
+      extra[0] = NAN;
+      extra[1] = NAN;
+      return;
+    }
+    const double dn = (double)n;
+    const long long tokens = A.group_tokens[u];
+    x[3] = (float)(a.ard / dn);
+    x[4] = (float)((double)(a.n_ts - a.distinct) / dn);   // sum over the buckets of (count - 1), / n
+    x[5] = tokens > 0 ? (float)((double)A.group_unique[u] / (double)tokens) : 0.f;
+    x[6] = (float)(a.rd / dn);
+    extra[0] = (float)((double)(a.h1 + a.h2) / dn);
+    extra[1] = (float)A.etg[u];
   }
-  const double dn = (double)n;
-  const double Ru = (double)a.helpful / dn;
-  A.user_y[u] = Ru >= 0.7 ? 1 : (Ru <= 0.3 ? 0 : -1);
-  double H = 0.0;
-  H = feat_plogp(H, a.h1, dn);
-  H = feat_plogp(H, a.h2, dn);
-  H = feat_plogp(H, a.h3, dn);
-  H = feat_plogp(H, a.h4, dn);
-  H = feat_plogp(H, a.h5, dn);
-  const long long tokens = A.group_tokens[u];
-  x[0] = (float)Ru;
-  x[1] = (float)H;
-  x[2] = (float)((double)(a.h1 + a.h5) / dn);
-  x[3] = (float)(a.ard / dn);
-  x[4] = (float)((double)(n_ts - a.distinct) / dn);   // sum over the buckets of (count - 1), / n
-  x[5] = tokens > 0 ? (float)((double)A.group_unique[u] / (double)tokens) : 0.f;
-  x[6] = (float)(a.rd / dn);
-  extra[0] = (float)((double)(a.h1 + a.h2) / dn);
-  extra[1] = (float)A.etg[u];
-}
-
-__global__ __launch_bounds__(256) void feat2_users_kernel(bbgr_feat_columns C,
-                                                          bbgr_feat_user_v2_args A,
-                                                          const int4 *packed, int *long_count,
-                                                          int *long_rows, int long_cap) {
-  const int u = blockIdx.x * 256 + threadIdx.x;
-  if (u >= C.n_users) return;
-  const int rb = A.u_indptr[u], re = A.u_indptr[u + 1];
-  if (re - rb > FEAT_LONG_ROW) {
-    const int pos = atomicAdd(long_count, 1);
-    if (pos < long_cap) long_rows[pos] = u;   // always, for an indptr that ends at n
-    return;
-  }
-  const int bb = A.b_indptr[u], be = A.b_indptr[u + 1];
-  UserAcc2 a;
-  feat2_user_acc(C, A, packed, rb, re, bb, be, 0, 1, a);
-  feat2_user_store(A, u, re - rb, be - bb, a);
-}
-
-__global__ __launch_bounds__(256) void feat2_users_long_kernel(bbgr_feat_columns C,
-                                                               bbgr_feat_user_v2_args A,
-                                                               const int4 *packed,
-                                                               const int *long_count,
-                                                               const int *long_rows,
-                                                               int long_cap) {
-  __shared__ double s_d[4];
-  __shared__ int s_i[4];
-  const int n_long = min(*long_count, long_cap);
-  for (int j = blockIdx.x; j < n_long; j += gridDim.x) {
-    const int u = long_rows[j];
-    const int rb = A.u_indptr[u], re = A.u_indptr[u + 1];
-    const int bb = A.b_indptr[u], be = A.b_indptr[u + 1];
-    UserAcc2 a;
-    feat2_user_acc(C, A, packed, rb, re, bb, be, threadIdx.x, 256, a);
-    a.helpful = feat_block_sum(a.helpful, s_i);
-    a.h1 = feat_block_sum(a.h1, s_i);
-    a.h2 = feat_block_sum(a.h2, s_i);
-    a.h3 = feat_block_sum(a.h3, s_i);
-    a.h4 = feat_block_sum(a.h4, s_i);
-    a.h5 = feat_block_sum(a.h5, s_i);
-    a.distinct = feat_block_sum(a.distinct, s_i);
-    a.ard = feat_block_sum(a.ard, s_d);
-    a.rd = feat_block_sum(a.rd, s_d);
-    if (threadIdx.x == 0) feat2_user_store(A, u, re - rb, be - bb, a);
-  }
-}
-
-// The long-row list of a pass that splits at `row`: the counter, then the list.
-static size_t feat2_long_bytes(long n, int row) {
-  return align_up(256 + sizeof(int) * (size_t)(n / row + 1));
-}
+};
 
 }  // namespace bbgr
 
 using namespace bbgr;
-
-#define V2_REQ(fn, cond, what) BBGR_REQUIRE_IN(fn, cond, what)
 
 // bbgr_text_unique_pooled, or (tools/text_bench.py) some of its launch groups
 // on a workspace the groups before them have filled.
@@ -454,25 +309,26 @@ static int text_unique_pooled(const char *fn, const bbgr_text_args *a, int64_t t
                               const int32_t *group, int32_t n_groups, int64_t *group_tokens,
                               int32_t *group_unique, uint8_t *group_recheck, int stages,
                               void *workspace, size_t *workspace_bytes, bbgr_stream_t stream) {
-  V2_REQ(fn, a, "null args");
-  V2_REQ(fn, n_groups >= 0 && n_groups < INT_MAX, "n_groups out of range (0 <= n_groups < 2^31 - 1)");
-  V2_REQ(fn, a->n >= 0 && a->n < 2147483647LL, "n out of range (n must be < 2^31 - 1)");
-  V2_REQ(fn, a->first >= 0 && a->last >= a->first && a->last - a->first < 2147483647LL,
-         "first / last out of range (0 <= first <= last, last - first < 2^31 - 1 bytes)");
-  V2_REQ(fn, total_tokens >= 0 && total_tokens <= (a->last - a->first + a->n) / 2,
-         "total_tokens out of range (at most (last - first + n) / 2)");
-  V2_REQ(fn, workspace_bytes, "null workspace_bytes");
-  if (a->n > 0) V2_REQ(fn, group, "null group");
-  if (a->n > 0 || n_groups > 0) V2_REQ(fn, a->totals, "null totals");
+  BBGR_REQUIRE_IN(fn, a, "null args");
+  BBGR_REQUIRE_IN(fn, n_groups >= 0 && n_groups < INT_MAX,
+                  "n_groups out of range (0 <= n_groups < 2^31 - 1)");
+  // text_check's three range checks of first and last in this entry's one wording
+  BBGR_REQUIRE_IN(fn, a->first >= 0 && a->last >= a->first && a->last - a->first < 2147483647LL,
+                  "first / last out of range (0 <= first <= last, last - first < 2^31 - 1 bytes)");
+  if (int rc = text_check(fn, a)) return rc;
+  BBGR_REQUIRE_IN(fn, total_tokens >= 0 && total_tokens <= (a->last - a->first + a->n) / 2,
+                  "total_tokens out of range (at most (last - first + n) / 2)");
+  if (a->n > 0) BBGR_REQUIRE_IN(fn, group, "null group");
   if (n_groups > 0) {
-    V2_REQ(fn, group_tokens, "null group_tokens");
-    V2_REQ(fn, group_unique, "null group_unique");
-    V2_REQ(fn, group_recheck, "null group_recheck");
+    BBGR_REQUIRE_IN(fn, a->totals, "null totals");
+    BBGR_REQUIRE_IN(fn, group_tokens, "null group_tokens");
+    BBGR_REQUIRE_IN(fn, group_unique, "null group_unique");
+    BBGR_REQUIRE_IN(fn, group_recheck, "null group_recheck");
   }
   const long n = (long)a->n;
   const int T = (int)total_tokens;
   const size_t nt = (size_t)T;
-  // the token stream's own workspace first (its checks of the other fields too)
+  // the token stream's own workspace first
   size_t base = 0;
   if (int rc = bbgr_text_unique_stages(a, total_tokens, BBGR_TEXT_STAGE_EMIT, nullptr, &base,
                                        stream))
@@ -493,21 +349,14 @@ static int text_unique_pooled(const char *fn, const bbgr_text_args *a, int64_t t
   const size_t off_g1 = align_up(base);
   const size_t off_g2 = off_g1 + align_up(sizeof(uint32_t) * nt);
   const size_t off_tmp = off_g2 + align_up(sizeof(uint32_t) * nt);
-  const size_t need = off_tmp + align_up(temp);
-  if (!workspace) {
-    *workspace_bytes = need;
-    return BBGR_OK;
-  }
-  if (*workspace_bytes < need) {
-    set_error("%s: workspace %zu < %zu bytes", fn, *workspace_bytes, need);
-    return BBGR_ERR_WORKSPACE;
-  }
+  bool query;
+  int rc = feat_workspace(fn, off_tmp + align_up(temp), workspace, workspace_bytes, &query);
+  if (rc || query) return rc;
   hipStream_t st = as_stream(stream);
   if (T > 0 && n > 0 && (stages & BBGR_TEXT_STAGE_EMIT)) {
     size_t nb = base;
-    if (int rc = bbgr_text_unique_stages(a, total_tokens, BBGR_TEXT_STAGE_EMIT, workspace, &nb,
-                                         stream))
-      return rc;
+    rc = bbgr_text_unique_stages(a, total_tokens, BBGR_TEXT_STAGE_EMIT, workspace, &nb, stream);
+    if (rc) return rc;
   }
   char *ws = static_cast<char *>(workspace);
   const TextWorkspace W = text_workspace(n, nt);
@@ -518,17 +367,7 @@ static int text_unique_pooled(const char *fn, const bbgr_text_args *a, int64_t t
   uint32_t *g1 = reinterpret_cast<uint32_t *>(ws + off_g1);
   uint32_t *g2 = reinterpret_cast<uint32_t *>(ws + off_g2);
   void *tmp = ws + off_tmp;
-  TextTokens K;
-  K.n = n;
-  K.total = T;
-  K.data = a->data;
-  K.offsets = reinterpret_cast<const long long *>(a->offsets);
-  K.first = (long)a->first;
-  K.last = (long)a->last;
-  K.tok_pos = reinterpret_cast<const uint32_t *>(ws + W.off_pos);
-  K.tok_rec = reinterpret_cast<const int *>(ws + W.off_rec);
-  K.tok_off = reinterpret_cast<const int *>(ws);
-  K.hash_mask = a->hash_mask ? a->hash_mask : ~0ull;
+  const TextTokens K = text_tokens(a, workspace, W, T);
   const unsigned tok_blocks = (unsigned)(((long)T + 255) / 256);
   if (T > 0 && n > 0 && (stages & BBGR_TEXT_STAGE_SORT)) {
     // by hash, then (stable) by group: equal (group, hash) pairs end side by
@@ -562,12 +401,7 @@ static int text_unique_pooled(const char *fn, const bbgr_text_args *a, int64_t t
                      (const int *)a->n_tokens, (const uint8_t *)a->recheck, group, n_groups,
                      reinterpret_cast<unsigned long long *>(group_tokens), group_recheck);
   BBGR_LAUNCHED("pool_records_kernel");
-  const long gb = ((long)n_groups + 255) / 256;
-  hipLaunchKernelGGL(pool_flagged_kernel, dim3((unsigned)(gb < 1024 ? gb : 1024)), dim3(256), 0,
-                     st, n_groups, (const uint8_t *)group_recheck,
-                     reinterpret_cast<long long *>(a->totals));
-  BBGR_LAUNCHED("pool_flagged_kernel");
-  return BBGR_OK;
+  return text_flag_total((long)n_groups, group_recheck, a->totals, st);
 }
 
 extern "C" int bbgr_text_unique_pooled(const bbgr_text_args *a, int64_t total_tokens,
@@ -587,7 +421,7 @@ extern "C" int bbgr_text_unique_pooled_stages(const bbgr_text_args *a, int64_t t
                                               void *workspace, size_t *workspace_bytes,
                                               bbgr_stream_t stream) {
   static const char *fn = "bbgr_text_unique_pooled_stages";
-  V2_REQ(fn, stages > 0 && stages <= BBGR_TEXT_STAGE_ALL, "stages out of range (1 .. 7)");
+  BBGR_REQUIRE_IN(fn, stages > 0 && stages <= BBGR_TEXT_STAGE_ALL, "stages out of range (1 .. 7)");
   return text_unique_pooled(fn, a, total_tokens, group, n_groups, group_tokens, group_unique,
                             group_recheck, stages, workspace, workspace_bytes, stream);
 }
@@ -596,12 +430,11 @@ extern "C" int bbgr_feat_lenlog(const bbgr_feat_columns *c, double *lenlog_sum, 
                                 size_t *workspace_bytes, bbgr_stream_t stream) {
   static const char *fn = "bbgr_feat_lenlog";
   if (int rc = feat_columns_ok(fn, c)) return rc;
-  V2_REQ(fn, workspace_bytes, "null workspace_bytes");
   bool query;
   int rc = feat_workspace(fn, align_up(sizeof(double) * LENLOG_GRID), workspace, workspace_bytes,
                           &query);
   if (rc || query) return rc;
-  V2_REQ(fn, lenlog_sum, "null lenlog_sum");
+  BBGR_REQUIRE_IN(fn, lenlog_sum, "null lenlog_sum");
   hipStream_t st = as_stream(stream);
   double *partial = static_cast<double *>(workspace);
   hipLaunchKernelGGL(feat2_lenlog_kernel, dim3(LENLOG_GRID), dim3(256), 0, st, (long)c->n,
@@ -618,29 +451,15 @@ extern "C" int bbgr_feat_item_means(const bbgr_feat_columns *c, const int32_t *i
                                     size_t *workspace_bytes, bbgr_stream_t stream) {
   static const char *fn = "bbgr_feat_item_means";
   if (int rc = feat_columns_ok(fn, c)) return rc;
-  V2_REQ(fn, workspace_bytes, "null workspace_bytes");
   bool query;
   int rc = feat_workspace(fn, feat_long_bytes((long)c->n), workspace, workspace_bytes, &query);
   if (rc || query) return rc;
   if (c->n_items == 0) return BBGR_OK;
-  V2_REQ(fn, i_indptr, "null i_indptr");
-  V2_REQ(fn, c->n == 0 || i_eid, "null i_eid");
-  V2_REQ(fn, item_mean, "null item_mean");
-  hipStream_t st = as_stream(stream);
-  int *long_count = static_cast<int *>(workspace);
-  int *long_rows = reinterpret_cast<int *>(static_cast<char *>(workspace) + 256);
-  const int long_cap = (int)(c->n / FEAT_LONG_ROW + 1);
-  BBGR_HIP(hipMemsetAsync(long_count, 0, sizeof(int), st));
-  hipLaunchKernelGGL(feat2_item_means_kernel, dim3((unsigned)((c->n_items + 255) / 256)),
-                     dim3(256), 0, st, *c, i_indptr, i_eid, item_mean, long_count, long_rows,
-                     long_cap);
-  BBGR_LAUNCHED("feat2_item_means_kernel");
-  if (c->n > FEAT_LONG_ROW) {
-    hipLaunchKernelGGL(feat2_item_means_long_kernel, dim3(FEAT_LONG_GRID), dim3(256), 0, st, *c,
-                       i_indptr, i_eid, item_mean, long_count, long_rows, long_cap);
-    BBGR_LAUNCHED("feat2_item_means_long_kernel");
-  }
-  return BBGR_OK;
+  BBGR_REQUIRE_IN(fn, i_indptr, "null i_indptr");
+  BBGR_REQUIRE_IN(fn, c->n == 0 || i_eid, "null i_eid");
+  BBGR_REQUIRE_IN(fn, item_mean, "null item_mean");
+  return feat_row_pass(fn, ItemMeansPass{{i_indptr}, *c, i_eid, item_mean}, c->n_items, (long)c->n,
+                       workspace, as_stream(stream));
 }
 
 extern "C" int bbgr_feat_gaps(const bbgr_feat_columns *c, const int32_t *u_indptr,
@@ -648,7 +467,6 @@ extern "C" int bbgr_feat_gaps(const bbgr_feat_columns *c, const int32_t *u_indpt
                               size_t *workspace_bytes, bbgr_stream_t stream) {
   static const char *fn = "bbgr_feat_gaps";
   if (int rc = feat_columns_ok(fn, c)) return rc;
-  V2_REQ(fn, workspace_bytes, "null workspace_bytes");
   const int n = (int)c->n, U = c->n_users;
   size_t t_sort = 0;
   if (n > 0) {
@@ -658,24 +476,20 @@ extern "C" int bbgr_feat_gaps(const bbgr_feat_columns *c, const int32_t *u_indpt
                                                      (double *)nullptr, n, U, seg_b, seg_e, 0, 64,
                                                      (hipStream_t) nullptr);
   }
-  const size_t off_d1 = feat2_long_bytes((long)n, GAP_SHORT_ROW);
+  const size_t off_d1 = feat_long_bytes((long)n, GAP_SHORT_ROW);
   const size_t off_d2 = off_d1 + align_up(sizeof(double) * (size_t)n);
   const size_t off_tmp = off_d2 + align_up(sizeof(double) * (size_t)n);
   bool query;
   int rc = feat_workspace(fn, off_tmp + align_up(t_sort), workspace, workspace_bytes, &query);
   if (rc || query) return rc;
   if (U == 0) return BBGR_OK;
-  V2_REQ(fn, u_indptr, "null u_indptr");
-  V2_REQ(fn, n == 0 || u_eid, "null u_eid");
-  V2_REQ(fn, etg, "null etg");
+  BBGR_REQUIRE_IN(fn, u_indptr, "null u_indptr");
+  BBGR_REQUIRE_IN(fn, n == 0 || u_eid, "null u_eid");
+  BBGR_REQUIRE_IN(fn, etg, "null etg");
   hipStream_t st = as_stream(stream);
   char *ws = static_cast<char *>(workspace);
-  int *long_count = reinterpret_cast<int *>(ws);
-  int *long_rows = reinterpret_cast<int *>(ws + 256);
-  const int long_cap = n / GAP_SHORT_ROW + 1;
   double *d1 = reinterpret_cast<double *>(ws + off_d1);
   double *d2 = reinterpret_cast<double *>(ws + off_d2);
-  BBGR_HIP(hipMemsetAsync(long_count, 0, sizeof(int), st));
   const RowBound rb_of{u_indptr, n, false}, re_of{u_indptr, n, true};
   if (n > 0) {
     hipLaunchKernelGGL(feat2_days_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, *c,
@@ -687,16 +501,7 @@ extern "C" int bbgr_feat_gaps(const bbgr_feat_columns *c, const int32_t *u_indpt
     BBGR_HIP(hipcub::DeviceSegmentedRadixSort::SortKeys(ws + off_tmp, tb, (const double *)d1, d2,
                                                         n, U, seg_b, seg_e, 0, 64, st));
   }
-  hipLaunchKernelGGL(feat2_gaps_kernel, dim3((unsigned)((U + 255) / 256)), dim3(256), 0, st, U,
-                     rb_of, re_of, (const double *)d2, etg, long_count, long_rows, long_cap);
-  BBGR_LAUNCHED("feat2_gaps_kernel");
-  if (n > GAP_SHORT_ROW) {
-    hipLaunchKernelGGL(feat2_gaps_long_kernel, dim3(FEAT_LONG_GRID), dim3(256), 0, st, rb_of,
-                       re_of, (const double *)d2, etg, (const int *)long_count,
-                       (const int *)long_rows, long_cap);
-    BBGR_LAUNCHED("feat2_gaps_long_kernel");
-  }
-  return BBGR_OK;
+  return feat_row_pass(fn, GapsPass{u_indptr, n, d2, etg}, U, (long)n, workspace, st);
 }
 
 extern "C" int bbgr_feat_users_v2(const bbgr_feat_columns *c, const bbgr_feat_user_v2_args *a,
@@ -704,8 +509,7 @@ extern "C" int bbgr_feat_users_v2(const bbgr_feat_columns *c, const bbgr_feat_us
                                   bbgr_stream_t stream) {
   static const char *fn = "bbgr_feat_users_v2";
   if (int rc = feat_columns_ok(fn, c)) return rc;
-  V2_REQ(fn, a, "null args");
-  V2_REQ(fn, workspace_bytes, "null workspace_bytes");
+  BBGR_REQUIRE_IN(fn, a, "null args");
   bool query;
   // the long-row list, then the packed records
   const size_t off_packed = feat_long_bytes((long)c->n);
@@ -713,39 +517,24 @@ extern "C" int bbgr_feat_users_v2(const bbgr_feat_columns *c, const bbgr_feat_us
                           workspace_bytes, &query);
   if (rc || query) return rc;
   if (c->n_users == 0) return BBGR_OK;
-  V2_REQ(fn, a->u_indptr, "null u_indptr");
-  V2_REQ(fn, a->b_indptr, "null b_indptr");
+  BBGR_REQUIRE_IN(fn, a->u_indptr, "null u_indptr");
+  BBGR_REQUIRE_IN(fn, a->b_indptr, "null b_indptr");
   if (c->n > 0) {
-    V2_REQ(fn, a->u_eid, "null u_eid");
-    V2_REQ(fn, a->b_bucket, "null b_bucket");
-    V2_REQ(fn, a->item_mean, "null item_mean");
+    BBGR_REQUIRE_IN(fn, a->u_eid, "null u_eid");
+    BBGR_REQUIRE_IN(fn, a->b_bucket, "null b_bucket");
+    BBGR_REQUIRE_IN(fn, a->item_mean, "null item_mean");
   }
-  V2_REQ(fn, a->group_tokens, "null group_tokens");
-  V2_REQ(fn, a->group_unique, "null group_unique");
-  V2_REQ(fn, a->etg, "null etg");
-  V2_REQ(fn, a->user_x, "null user_x");
-  V2_REQ(fn, a->user_y, "null user_y");
-  V2_REQ(fn, a->total_reviews, "null total_reviews");
-  V2_REQ(fn, a->helpful_reviews, "null helpful_reviews");
-  V2_REQ(fn, a->user_extra, "null user_extra");
+  BBGR_REQUIRE_IN(fn, a->group_tokens, "null group_tokens");
+  BBGR_REQUIRE_IN(fn, a->group_unique, "null group_unique");
+  BBGR_REQUIRE_IN(fn, a->etg, "null etg");
+  BBGR_REQUIRE_IN(fn, a->user_x, "null user_x");
+  BBGR_REQUIRE_IN(fn, a->user_y, "null user_y");
+  BBGR_REQUIRE_IN(fn, a->total_reviews, "null total_reviews");
+  BBGR_REQUIRE_IN(fn, a->helpful_reviews, "null helpful_reviews");
+  BBGR_REQUIRE_IN(fn, a->user_extra, "null user_extra");
   hipStream_t st = as_stream(stream);
-  int *long_count = static_cast<int *>(workspace);
-  int *long_rows = reinterpret_cast<int *>(static_cast<char *>(workspace) + 256);
-  const int long_cap = (int)(c->n / FEAT_LONG_ROW + 1);
-  BBGR_HIP(hipMemsetAsync(long_count, 0, sizeof(int), st));
   int4 *packed = reinterpret_cast<int4 *>(static_cast<char *>(workspace) + off_packed);
-  if (c->n > 0) {
-    hipLaunchKernelGGL(feat2_pack_kernel, dim3((unsigned)((c->n + 255) / 256)), dim3(256), 0, st,
-                       *c, packed);
-    BBGR_LAUNCHED("feat2_pack_kernel");
-  }
-  hipLaunchKernelGGL(feat2_users_kernel, dim3((unsigned)((c->n_users + 255) / 256)), dim3(256), 0,
-                     st, *c, *a, packed, long_count, long_rows, long_cap);
-  BBGR_LAUNCHED("feat2_users_kernel");
-  if (c->n > FEAT_LONG_ROW) {
-    hipLaunchKernelGGL(feat2_users_long_kernel, dim3(FEAT_LONG_GRID), dim3(256), 0, st, *c, *a,
-                       packed, long_count, long_rows, long_cap);
-    BBGR_LAUNCHED("feat2_users_long_kernel");
-  }
-  return BBGR_OK;
+  if ((rc = feat_pack<true>(c, packed, st))) return rc;
+  return feat_row_pass(fn, UsersV2Pass{{a->u_indptr}, *c, *a, packed}, c->n_users, (long)c->n,
+                       workspace, st);
 }

@@ -403,26 +403,24 @@ static long split_tiles(long n) { return (n + SPLIT_TILE - 1) / SPLIT_TILE; }
 
 using namespace bbgr;
 
-#define SPLIT_REQ(fn, cond, what) BBGR_REQUIRE_IN(fn, cond, what)
-
 extern "C" int bbgr_md5_pair_hash(int64_t n, const int32_t *user, const int32_t *item,
                                   const uint8_t *user_data, const int64_t *user_offsets,
                                   int32_t n_users, const uint8_t *item_data,
                                   const int64_t *item_offsets, int32_t n_items,
                                   const uint8_t *keep, uint32_t *hash32, bbgr_stream_t stream) {
   static const char *fn = "bbgr_md5_pair_hash";
-  SPLIT_REQ(fn, n >= 0 && n < 2147483647LL, "n out of range (n must be < 2^31 - 1)");
-  SPLIT_REQ(fn, n_users >= 0 && n_users < INT_MAX, "n_users out of range");
-  SPLIT_REQ(fn, n_items >= 0 && n_items < INT_MAX, "n_items out of range");
+  BBGR_REQUIRE_IN(fn, n >= 0 && n < 2147483647LL, "n out of range (n must be < 2^31 - 1)");
+  BBGR_REQUIRE_IN(fn, n_users >= 0 && n_users < INT_MAX, "n_users out of range");
+  BBGR_REQUIRE_IN(fn, n_items >= 0 && n_items < INT_MAX, "n_items out of range");
   if (n == 0) return BBGR_OK;
-  SPLIT_REQ(fn, n_users > 0 && n_items > 0, "records but no n_users / n_items");
-  SPLIT_REQ(fn, user, "null user");
-  SPLIT_REQ(fn, item, "null item");
-  SPLIT_REQ(fn, user_data, "null user_data");
-  SPLIT_REQ(fn, user_offsets, "null user_offsets");
-  SPLIT_REQ(fn, item_data, "null item_data");
-  SPLIT_REQ(fn, item_offsets, "null item_offsets");
-  SPLIT_REQ(fn, hash32, "null hash32");
+  BBGR_REQUIRE_IN(fn, n_users > 0 && n_items > 0, "records but no n_users / n_items");
+  BBGR_REQUIRE_IN(fn, user, "null user");
+  BBGR_REQUIRE_IN(fn, item, "null item");
+  BBGR_REQUIRE_IN(fn, user_data, "null user_data");
+  BBGR_REQUIRE_IN(fn, user_offsets, "null user_offsets");
+  BBGR_REQUIRE_IN(fn, item_data, "null item_data");
+  BBGR_REQUIRE_IN(fn, item_offsets, "null item_offsets");
+  BBGR_REQUIRE_IN(fn, hash32, "null hash32");
   Md5Params P;
   P.n = (long)n;
   P.user = user;
@@ -444,39 +442,32 @@ extern "C" int bbgr_md5_pair_hash(int64_t n, const int32_t *user, const int32_t 
 extern "C" int bbgr_split_edges(const bbgr_split_args *a, void *workspace,
                                 size_t *workspace_bytes, bbgr_stream_t stream) {
   static const char *fn = "bbgr_split_edges";
-  SPLIT_REQ(fn, a, "null args");
-  SPLIT_REQ(fn, a->n >= 0 && a->n < 2147483647LL, "n out of range (n must be < 2^31 - 1)");
-  SPLIT_REQ(fn, a->n_users >= 0 && a->n_users < INT_MAX, "n_users out of range");
-  SPLIT_REQ(fn, a->n_items >= 0 && a->n_items < INT_MAX, "n_items out of range");
-  SPLIT_REQ(fn, a->thr_val <= SPLIT_THR_MAX, "thr_val > 2^32");
-  SPLIT_REQ(fn, a->thr_train <= a->thr_val, "thr_train > thr_val");
+  BBGR_REQUIRE_IN(fn, a, "null args");
+  BBGR_REQUIRE_IN(fn, a->n >= 0 && a->n < 2147483647LL, "n out of range (n must be < 2^31 - 1)");
+  BBGR_REQUIRE_IN(fn, a->n_users >= 0 && a->n_users < INT_MAX, "n_users out of range");
+  BBGR_REQUIRE_IN(fn, a->n_items >= 0 && a->n_items < INT_MAX, "n_items out of range");
+  BBGR_REQUIRE_IN(fn, a->thr_val <= SPLIT_THR_MAX, "thr_val > 2^32");
+  BBGR_REQUIRE_IN(fn, a->thr_train <= a->thr_val, "thr_train > thr_val");
   if (a->n > 0) {
-    SPLIT_REQ(fn, a->n_users > 0 && a->n_items > 0, "records but no n_users / n_items");
-    SPLIT_REQ(fn, a->user, "null user");
-    SPLIT_REQ(fn, a->item, "null item");
-    SPLIT_REQ(fn, a->positive || a->rating, "null positive and null rating");
-    SPLIT_REQ(fn, a->hash32, "null hash32");
-    SPLIT_REQ(fn, a->user_map, "null user_map");
-    SPLIT_REQ(fn, a->item_map, "null item_map");
-    SPLIT_REQ(fn, a->user_src, "null user_src");
-    SPLIT_REQ(fn, a->item_src, "null item_src");
-    SPLIT_REQ(fn, a->edges, "null edges");
-    SPLIT_REQ(fn, a->ld_edges >= a->n, "ld_edges < n");
-    SPLIT_REQ(fn, a->counts, "null counts");
+    BBGR_REQUIRE_IN(fn, a->n_users > 0 && a->n_items > 0, "records but no n_users / n_items");
+    BBGR_REQUIRE_IN(fn, a->user, "null user");
+    BBGR_REQUIRE_IN(fn, a->item, "null item");
+    BBGR_REQUIRE_IN(fn, a->positive || a->rating, "null positive and null rating");
+    BBGR_REQUIRE_IN(fn, a->hash32, "null hash32");
+    BBGR_REQUIRE_IN(fn, a->user_map, "null user_map");
+    BBGR_REQUIRE_IN(fn, a->item_map, "null item_map");
+    BBGR_REQUIRE_IN(fn, a->user_src, "null user_src");
+    BBGR_REQUIRE_IN(fn, a->item_src, "null item_src");
+    BBGR_REQUIRE_IN(fn, a->edges, "null edges");
+    BBGR_REQUIRE_IN(fn, a->ld_edges >= a->n, "ld_edges < n");
+    BBGR_REQUIRE_IN(fn, a->counts, "null counts");
   }
-  SPLIT_REQ(fn, workspace_bytes, "null workspace_bytes");
   const long n = (long)a->n, n_tiles = split_tiles(n);
   const size_t off_tiles = split_code_bytes(n);
-  const size_t need = off_tiles + align_up(sizeof(int) * SPLIT_NC * (size_t)(n_tiles + 1));
-  if (!workspace) {
-    *workspace_bytes = need;
-    return BBGR_OK;
-  }
-  if (*workspace_bytes < need) {
-    set_error("%s: workspace %zu < %zu bytes", fn, *workspace_bytes, need);
-    return BBGR_ERR_WORKSPACE;
-  }
-  if (n == 0) return BBGR_OK;
+  bool query;
+  int rc = feat_workspace(fn, off_tiles + align_up(sizeof(int) * SPLIT_NC * (size_t)(n_tiles + 1)),
+                          workspace, workspace_bytes, &query);
+  if (rc || query || n == 0) return rc;
   hipStream_t st = as_stream(stream);
   uint8_t *code = static_cast<uint8_t *>(workspace);
   int *tiles = reinterpret_cast<int *>(static_cast<char *>(workspace) + off_tiles);

@@ -2,7 +2,9 @@
 // the letter rule, a record's clamped byte range, the cursor that reads a
 // token's normalised bytes forward from its start, the token stream of
 // bbgr_text_unique's EMIT stage and where that stage leaves it in the
-// workspace.
+// workspace, and the rule of the distinct count (per record there, per group
+// here): the comparison of two tokens, the count per run of equal keys in a
+// wave, the clamped row bounds of the segmented sorts, the flag total.
 #pragma once
 
 #include "common.h"
@@ -81,6 +83,52 @@ __device__ __forceinline__ TokenCursor text_cursor(const TextTokens &T, long tok
   return TokenCursor{T.data, q < end ? q : end, end, false};
 }
 
+// Whether the normalised bytes of tokens a and b differ, read side by side to
+// their ends.
+__device__ __forceinline__ bool text_tokens_differ(const TextTokens &T, long a, long b) {
+  TokenCursor ca = text_cursor(T, a), cb = text_cursor(T, b);
+  for (;;) {
+    const int x = ca.next(), y = cb.next();
+    if (x != y) return true;
+    if (x < 0) return false;
+  }
+}
+
+// The distinct count of one lane per sorted slot, called by the whole wave:
+// key is the slot's record or group (live: it has one; every other lane holds
+// a key no live lane has), opens whether the slot begins a run of equal
+// tokens. The lanes of a wave that share a key add their opening slots to
+// count[key] with one integer atomic, issued by the first of them.
+__device__ __forceinline__ void text_count_opens(int key, bool live, bool opens, int *count) {
+  const int lane = threadIdx.x & 63;
+  const int left = __shfl_up(key, 1);
+  const unsigned long long heads = __ballot(lane == 0 || key != left), open_m = __ballot(opens);
+  if (live && (heads >> lane & 1ull)) {
+    const unsigned long long after = lane == 63 ? 0ull : heads >> (lane + 1);
+    const int len = after ? __ffsll((long long)after) : 64 - lane;   // lanes of this key here
+    const unsigned long long mine = (len == 64 ? ~0ull : (1ull << len) - 1ull) << lane;
+    const int cnt = __popcll(open_m & mine);
+    if (cnt) atomicAdd(count + key, cnt);
+  }
+}
+
+// Row bounds of a segmented sort from an indptr (a CSR's, or the token
+// offsets): row r is [begin(r), end(r)), both clamped into [0, n] and end(r)
+// >= begin(r), so no indptr, however wrong (a workspace no scan has filled),
+// sends the sort outside its keys.
+struct RowBound {
+  const int *indptr;
+  int n;
+  bool end;
+  __host__ __device__ __forceinline__ int clamp(int v) const { return v < 0 ? 0 : (v < n ? v : n); }
+  __host__ __device__ __forceinline__ int operator()(int r) const {
+    const int b = clamp(indptr[r]);
+    if (!end) return b;
+    const int e = clamp(indptr[r + 1]);
+    return e < b ? b : e;
+  }
+};
+
 // The carve of bbgr_text_unique's workspace up to the sort's own temporary
 // storage: token offsets [n + 1], then per token its record, its start, the
 // hash and the token index before (k1, v1) and after (k2, v2) the sort.
@@ -99,5 +147,30 @@ inline TextWorkspace text_workspace(long n, size_t nt) {
   w.off_tmp = w.off_v2 + align_up(sizeof(uint32_t) * nt);
   return w;
 }
+
+// The token stream of T tokens that the EMIT stage leaves (or will leave) in
+// `workspace`.
+inline TextTokens text_tokens(const bbgr_text_args *a, void *workspace, const TextWorkspace &W,
+                              int T) {
+  const char *ws = static_cast<const char *>(workspace);
+  TextTokens K;
+  K.n = (long)a->n;
+  K.total = T;
+  K.data = a->data;
+  K.offsets = reinterpret_cast<const long long *>(a->offsets);
+  K.first = (long)a->first;
+  K.last = (long)a->last;
+  K.tok_pos = reinterpret_cast<const uint32_t *>(ws + W.off_pos);
+  K.tok_rec = reinterpret_cast<const int *>(ws + W.off_rec);
+  K.tok_off = reinterpret_cast<const int *>(ws);
+  K.hash_mask = a->hash_mask ? a->hash_mask : ~0ull;
+  return K;
+}
+
+// text.hip: the checks of bbgr_text_args every entry point that takes one
+// shares, and totals[1] += the number of non-zero flag[0 .. n) (one launch of
+// text_recheck_total_kernel).
+int text_check(const char *fn, const bbgr_text_args *a);
+int text_flag_total(long n, const uint8_t *flag, int64_t *totals, hipStream_t st);
 
 }  // namespace bbgr

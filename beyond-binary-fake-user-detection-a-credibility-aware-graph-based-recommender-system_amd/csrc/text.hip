@@ -153,34 +153,16 @@ __global__ __launch_bounds__(256) void text_verify_kernel(TextTokens T,
                                                           const uint32_t *vals, int *n_unique,
                                                           uint8_t *recheck) {
   const long j = (long)blockIdx.x * 256 + threadIdx.x;
-  const int lane = threadIdx.x & 63;
   int rec = j < text_live_tokens(T) ? T.tok_rec[j] : -1;   // the same before and after the sort
   if (rec >= T.n) rec = -1;
   const bool live = rec >= 0;
   bool opens = false;
   if (live) {
     opens = j == 0 || j == (long)T.tok_off[rec] || keys[j] != keys[j - 1];
-    if (!opens) {
-      TokenCursor a = text_cursor(T, vals[j]), b = text_cursor(T, vals[j - 1]);
-      for (;;) {
-        const int x = a.next(), y = b.next();
-        if (x != y) {
-          recheck[rec] = 1;   // every writer stores the same value
-          break;
-        }
-        if (x < 0) break;
-      }
-    }
+    // every writer stores the same value
+    if (!opens && text_tokens_differ(T, vals[j], vals[j - 1])) recheck[rec] = 1;
   }
-  const int left = __shfl_up(rec, 1);
-  const unsigned long long heads = __ballot(lane == 0 || rec != left), open_m = __ballot(opens);
-  if (live && (heads >> lane & 1ull)) {
-    const unsigned long long after = lane == 63 ? 0ull : heads >> (lane + 1);
-    const int len = after ? __ffsll((long long)after) : 64 - lane;   // lanes of this record here
-    const unsigned long long mine = (len == 64 ? ~0ull : (1ull << len) - 1ull) << lane;
-    const int cnt = __popcll(open_m & mine);
-    if (cnt) atomicAdd(n_unique + rec, cnt);
-  }
+  text_count_opens(rec, live, opens, n_unique);
 }
 
 __global__ __launch_bounds__(256) void text_recheck_total_kernel(long n, const uint8_t *recheck,
@@ -194,25 +176,8 @@ __global__ __launch_bounds__(256) void text_recheck_total_kernel(long n, const u
     atomicAdd(reinterpret_cast<unsigned long long *>(totals) + 1, (unsigned long long)cnt);
 }
 
-// Segment bounds of the sort, from the token offsets: record r's tokens are
-// [begin(r), end(r)), both clamped into [0, total] and end(r) >= begin(r), so
-// no offset, however wrong (a workspace no scan has filled), sends the sort
-// outside the token arrays.
-struct SegBound {
-  const int *tok_off;
-  int total;
-  bool end;
-  __host__ __device__ __forceinline__ int clamp(int v) const {
-    return v < 0 ? 0 : (v < total ? v : total);
-  }
-  __host__ __device__ __forceinline__ int operator()(int r) const {
-    const int b = clamp(tok_off[r]);
-    if (!end) return b;
-    const int e = clamp(tok_off[r + 1]);
-    return e < b ? b : e;
-  }
-};
-typedef hipcub::TransformInputIterator<int, SegBound, hipcub::CountingInputIterator<int>> SegIter;
+// Segment bounds of the sort: record r's tokens, by the token offsets.
+typedef hipcub::TransformInputIterator<int, RowBound, hipcub::CountingInputIterator<int>> SegIter;
 
 static unsigned text_walk_blocks(long n) {
   const long b = (n + TEXT_WAVES - 1) / TEXT_WAVES;
@@ -236,30 +201,35 @@ static TextParams text_params(const bbgr_text_args *a) {
   return P;
 }
 
-}  // namespace bbgr
-
-using namespace bbgr;
-
-#define TEXT_REQ(fn, cond, what) BBGR_REQUIRE_IN(fn, cond, what)
-
-// The checks the two entry points share.
-static int text_check(const char *fn, const bbgr_text_args *a) {
-  TEXT_REQ(fn, a, "null args");
-  TEXT_REQ(fn, a->n >= 0 && a->n < 2147483647LL, "n out of range (n must be < 2^31 - 1)");
-  TEXT_REQ(fn, a->first >= 0, "first < 0");
-  TEXT_REQ(fn, a->last >= a->first, "last < first");
-  TEXT_REQ(fn, a->last - a->first < 2147483647LL,
-           "last - first out of range (must be < 2^31 - 1 bytes)");
+int text_check(const char *fn, const bbgr_text_args *a) {
+  BBGR_REQUIRE_IN(fn, a, "null args");
+  BBGR_REQUIRE_IN(fn, a->n >= 0 && a->n < 2147483647LL, "n out of range (n must be < 2^31 - 1)");
+  BBGR_REQUIRE_IN(fn, a->first >= 0, "first < 0");
+  BBGR_REQUIRE_IN(fn, a->last >= a->first, "last < first");
+  BBGR_REQUIRE_IN(fn, a->last - a->first < 2147483647LL,
+                  "last - first out of range (must be < 2^31 - 1 bytes)");
   if (a->n > 0) {
-    TEXT_REQ(fn, a->data, "null data");
-    TEXT_REQ(fn, a->offsets, "null offsets");
-    TEXT_REQ(fn, a->n_tokens, "null n_tokens");
-    TEXT_REQ(fn, a->n_unique_tokens, "null n_unique_tokens");
-    TEXT_REQ(fn, a->recheck, "null recheck");
-    TEXT_REQ(fn, a->totals, "null totals");
+    BBGR_REQUIRE_IN(fn, a->data, "null data");
+    BBGR_REQUIRE_IN(fn, a->offsets, "null offsets");
+    BBGR_REQUIRE_IN(fn, a->n_tokens, "null n_tokens");
+    BBGR_REQUIRE_IN(fn, a->n_unique_tokens, "null n_unique_tokens");
+    BBGR_REQUIRE_IN(fn, a->recheck, "null recheck");
+    BBGR_REQUIRE_IN(fn, a->totals, "null totals");
   }
   return BBGR_OK;
 }
+
+int text_flag_total(long n, const uint8_t *flag, int64_t *totals, hipStream_t st) {
+  const long blocks = (n + 255) / 256;
+  hipLaunchKernelGGL(text_recheck_total_kernel, dim3((unsigned)(blocks < 1024 ? blocks : 1024)),
+                     dim3(256), 0, st, n, flag, reinterpret_cast<long long *>(totals));
+  BBGR_LAUNCHED("text_recheck_total_kernel");
+  return BBGR_OK;
+}
+
+}  // namespace bbgr
+
+using namespace bbgr;
 
 extern "C" int bbgr_text_count(const bbgr_text_args *a, bbgr_stream_t stream) {
   static const char *fn = "bbgr_text_count";
@@ -280,9 +250,8 @@ static int text_unique(const char *fn, const bbgr_text_args *a, int64_t total_to
   if (int rc = text_check(fn, a)) return rc;
   // inside a record two tokens have a byte between them: a record of len bytes
   // holds at most (len + 1) / 2 tokens; a record's edge separates for free
-  TEXT_REQ(fn, total_tokens >= 0 && total_tokens <= (a->last - a->first + a->n) / 2,
-           "total_tokens out of range (at most (last - first + n) / 2)");
-  TEXT_REQ(fn, workspace_bytes, "null workspace_bytes");
+  BBGR_REQUIRE_IN(fn, total_tokens >= 0 && total_tokens <= (a->last - a->first + a->n) / 2,
+                  "total_tokens out of range (at most (last - first + n) / 2)");
   const long n = (long)a->n;
   const int T = (int)total_tokens;
   const size_t nt = (size_t)T;
@@ -291,48 +260,28 @@ static int text_unique(const char *fn, const bbgr_text_args *a, int64_t total_to
     (void)hipcub::DeviceScan::InclusiveSum(nullptr, t_scan, (const int *)nullptr, (int *)nullptr,
                                            (int)n, (hipStream_t) nullptr);
     const hipcub::CountingInputIterator<int> rec(0);
-    const SegIter seg_b(rec, SegBound{nullptr, T, false}), seg_e(rec, SegBound{nullptr, T, true});
+    const SegIter seg_b(rec, RowBound{nullptr, T, false}), seg_e(rec, RowBound{nullptr, T, true});
     (void)hipcub::DeviceSegmentedRadixSort::SortPairs(
         nullptr, t_sort, (const unsigned long long *)nullptr, (unsigned long long *)nullptr,
         (const uint32_t *)nullptr, (uint32_t *)nullptr, T, (int)n, seg_b, seg_e, 0, 64,
         (hipStream_t) nullptr);
   }
   const TextWorkspace W = text_workspace(n, nt);
-  const size_t off_rec = W.off_rec, off_pos = W.off_pos, off_k1 = W.off_k1, off_k2 = W.off_k2,
-               off_v1 = W.off_v1, off_v2 = W.off_v2, off_tmp = W.off_tmp;
   const size_t temp = t_scan > t_sort ? t_scan : t_sort;
-  const size_t need = off_tmp + align_up(temp);
-  if (!workspace) {
-    *workspace_bytes = need;
-    return BBGR_OK;
-  }
-  if (*workspace_bytes < need) {
-    set_error("%s: workspace %zu < %zu bytes", fn, *workspace_bytes, need);
-    return BBGR_ERR_WORKSPACE;
-  }
-  if (n == 0) return BBGR_OK;
+  bool query;
+  int rc = feat_workspace(fn, W.off_tmp + align_up(temp), workspace, workspace_bytes, &query);
+  if (rc || query || n == 0) return rc;
   hipStream_t st = as_stream(stream);
   char *ws = static_cast<char *>(workspace);
   int *tok_off = reinterpret_cast<int *>(ws);
-  int *tok_rec = reinterpret_cast<int *>(ws + off_rec);
-  uint32_t *tok_pos = reinterpret_cast<uint32_t *>(ws + off_pos);
-  unsigned long long *k1 = reinterpret_cast<unsigned long long *>(ws + off_k1);
-  unsigned long long *k2 = reinterpret_cast<unsigned long long *>(ws + off_k2);
-  uint32_t *v1 = reinterpret_cast<uint32_t *>(ws + off_v1);
-  uint32_t *v2 = reinterpret_cast<uint32_t *>(ws + off_v2);
-  void *tmp = ws + off_tmp;
-
-  TextTokens K;
-  K.n = n;
-  K.total = T;
-  K.data = a->data;
-  K.offsets = reinterpret_cast<const long long *>(a->offsets);
-  K.first = (long)a->first;
-  K.last = (long)a->last;
-  K.tok_pos = tok_pos;
-  K.tok_rec = tok_rec;
-  K.tok_off = tok_off;
-  K.hash_mask = a->hash_mask ? a->hash_mask : ~0ull;
+  int *tok_rec = reinterpret_cast<int *>(ws + W.off_rec);
+  uint32_t *tok_pos = reinterpret_cast<uint32_t *>(ws + W.off_pos);
+  unsigned long long *k1 = reinterpret_cast<unsigned long long *>(ws + W.off_k1);
+  unsigned long long *k2 = reinterpret_cast<unsigned long long *>(ws + W.off_k2);
+  uint32_t *v1 = reinterpret_cast<uint32_t *>(ws + W.off_v1);
+  uint32_t *v2 = reinterpret_cast<uint32_t *>(ws + W.off_v2);
+  void *tmp = ws + W.off_tmp;
+  const TextTokens K = text_tokens(a, workspace, W, T);
   const unsigned tok_blocks = (unsigned)(((long)T + 255) / 256);
   if (T > 0 && (stages & BBGR_TEXT_STAGE_EMIT)) {
     // token offsets: tok_off[0] = 0, tok_off[r + 1] = n_tokens[0] + .. + n_tokens[r]
@@ -353,7 +302,7 @@ static int text_unique(const char *fn, const bbgr_text_args *a, int64_t total_to
   }
   if (T > 0 && (stages & BBGR_TEXT_STAGE_SORT)) {
     const hipcub::CountingInputIterator<int> rec(0);
-    const SegIter seg_b(rec, SegBound{tok_off, T, false}), seg_e(rec, SegBound{tok_off, T, true});
+    const SegIter seg_b(rec, RowBound{tok_off, T, false}), seg_e(rec, RowBound{tok_off, T, true});
     size_t tb = temp;
     BBGR_HIP(hipcub::DeviceSegmentedRadixSort::SortPairs(
         tmp, tb, (const unsigned long long *)k1, k2, (const uint32_t *)v1, v2, T, (int)n, seg_b,
@@ -368,11 +317,7 @@ static int text_unique(const char *fn, const bbgr_text_args *a, int64_t total_to
                        a->recheck);
     BBGR_LAUNCHED("text_verify_kernel");
   }
-  const long rb = (n + 255) / 256;
-  hipLaunchKernelGGL(text_recheck_total_kernel, dim3((unsigned)(rb < 1024 ? rb : 1024)), dim3(256),
-                     0, st, n, (const uint8_t *)a->recheck, reinterpret_cast<long long *>(a->totals));
-  BBGR_LAUNCHED("text_recheck_total_kernel");
-  return BBGR_OK;
+  return text_flag_total(n, a->recheck, a->totals, st);
 }
 
 extern "C" int bbgr_text_unique(const bbgr_text_args *a, int64_t total_tokens, void *workspace,
@@ -385,6 +330,6 @@ extern "C" int bbgr_text_unique_stages(const bbgr_text_args *a, int64_t total_to
                                        int32_t stages, void *workspace, size_t *workspace_bytes,
                                        bbgr_stream_t stream) {
   static const char *fn = "bbgr_text_unique_stages";
-  TEXT_REQ(fn, stages > 0 && stages <= BBGR_TEXT_STAGE_ALL, "stages out of range (1 .. 7)");
+  BBGR_REQUIRE_IN(fn, stages > 0 && stages <= BBGR_TEXT_STAGE_ALL, "stages out of range (1 .. 7)");
   return text_unique(fn, a, total_tokens, stages, workspace, workspace_bytes, stream);
 }
