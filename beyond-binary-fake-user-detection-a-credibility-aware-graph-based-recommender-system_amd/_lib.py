@@ -249,6 +249,25 @@ class TextArgs(ctypes.Structure):
     ]
 
 
+class JsonlArgs(ctypes.Structure):
+    """bbgr_jsonl_args (bbgr_jsonl_count .. bbgr_jsonl_write)."""
+    _fields_ = [
+        ("n_bytes", c_int64), ("data", c_void_p), ("n_lines", c_int64), ("line_end", c_void_p),
+        ("item_key", c_void_p), ("item_key_len", c_int32),
+        ("status", c_void_p), ("rating", c_void_p), ("helpful_vote", c_void_p),
+        ("verified", c_void_p), ("timestamp", c_void_p), ("ts_valid", c_void_p),
+        ("sizes", c_void_p), ("spos", c_void_p), ("totals", c_void_p), ("offs", c_void_p),
+        ("side", c_void_p), ("side_bytes", c_int64),
+        ("n_records", c_int64), ("user_bytes", c_int64), ("item_bytes", c_int64),
+        ("text_bytes", c_int64),
+        ("out_rating", c_void_p), ("out_helpful", c_void_p), ("out_verified", c_void_p),
+        ("out_timestamp", c_void_p), ("out_ts_valid", c_void_p),
+        ("user_data", c_void_p), ("user_off", c_void_p),
+        ("item_data", c_void_p), ("item_off", c_void_p),
+        ("text_data", c_void_p), ("text_off", c_void_p),
+    ]
+
+
 class Pcg64State(ctypes.Structure):
     """bbgr_pcg64: numpy's PCG64 bit_generator.state (128-bit state and
     increment as two 64-bit halves, the buffered 32-bit output)."""
@@ -425,6 +444,15 @@ _SIGNATURES = {
                         _P], c_int32),
     "bbgr_feat_users_v2": ([ctypes.POINTER(FeatColumns), ctypes.POINTER(FeatUserV2Args), _P,
                             ctypes.POINTER(c_size_t), _P], c_int32),
+    "bbgr_jsonl_count": ([ctypes.POINTER(JsonlArgs), _P], c_int32),
+    "bbgr_jsonl_lines": ([ctypes.POINTER(JsonlArgs), _P, ctypes.POINTER(c_size_t), _P], c_int32),
+    "bbgr_jsonl_scan": ([ctypes.POINTER(JsonlArgs), _P], c_int32),
+    "bbgr_jsonl_offsets": ([ctypes.POINTER(JsonlArgs), _P, ctypes.POINTER(c_size_t), _P], c_int32),
+    "bbgr_jsonl_write": ([ctypes.POINTER(JsonlArgs), _P], c_int32),
+    "bbgr_ids_number": ([c_int64, _P, _P, c_int64, c_uint64, _P, _P, _P, _P,
+                         ctypes.POINTER(c_size_t), _P], c_int32),
+    "bbgr_ids_table": ([c_int64, _P, c_int64, _P, _P, c_int64, _P, _P, c_int64, _P,
+                        ctypes.POINTER(c_size_t), _P], c_int32),
     # blueprint names, thin forms of the entry points above
     "bbgr_spmm_f32": ([ctypes.POINTER(CsrStruct), _P, c_int64, _P, c_int64, c_int32, _P, _P,
                        _P, c_float, _P], c_int32),

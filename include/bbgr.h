@@ -1542,6 +1542,126 @@ int bbgr_feat_users_v2(const bbgr_feat_columns *c, const bbgr_feat_user_v2_args 
                        void *workspace, size_t *workspace_bytes, bbgr_stream_t stream);
 
 /* ------------------------------------------------------------------------- */
+/* The review dump (one JSON object per line) -> per-record columns, id bytes  */
+/* and text bytes (features.review_columns_from_jsonl over bytes), and the     */
+/* numbering of id strings by first appearance. Appended; the ABI stays 12.    */
+/* Integer and exact-double work only: two calls give the same bits.           */
+/* ------------------------------------------------------------------------- */
+/* The rule over bytes. '\n' and '\r' both end a line; a last line without a   */
+/* terminator counts; a line of only spaces and tabs is blank. Per line: the   */
+/* string mask from the quotes and the parity of the backslash runs before     */
+/* them, the bracket depth outside strings; a ':' at depth 1 outside strings   */
+/* ends a top-level key, the string before it; the last occurrence of a key    */
+/* wins; deeper keys are ignored. The keys read: user_id, item_key, rating,    */
+/* helpful_vote, verified_purchase, timestamp, title, text. Vouched value      */
+/* forms: a string of well-formed UTF-8 (Python's strict decoder) without a    */
+/* raw byte below 0x20 and with the escapes \" \\ \/ \b \f \n \r \t \uXXXX (a  */
+/* high + low \u surrogate pair is one 4-byte code point, a lone surrogate its */
+/* 3 surrogatepass bytes); for helpful_vote and timestamp -?(0|[1-9][0-9]*) of */
+/* at most 18 digits (helpful_vote inside int32), null or missing = 0 (and     */
+/* ts_valid 0); for rating -?(0|[1-9][0-9]*)(\.[0-9]+)? of at most 15 digits   */
+/* and no negative zero, the value (double)digits / 10^k cast once to float,   */
+/* null or missing skips the record; true / false / null for                   */
+/* verified_purchase; a string or null for title and text; a string for the    */
+/* ids, where null, missing or "" skips the record. Every value read ends at a */
+/* blank, ',' or '}' inside the line. Every other form, a top-level key that holds a backslash, a     */
+/* line that does not open with '{', a byte below 0x20 (but a tab outside      */
+/* strings), a backslash outside strings, an unterminated string, unbalanced   */
+/* brackets, a top-level close other than '}' and bytes after it flag the      */
+/* line: status 3, for the caller to parse on the host. Not detected:          */
+/* malformed JSON that no value read depends on, while strings and brackets    */
+/* balance.                                                                    */
+/* Line status: 0 blank, 1 skipped, 2 kept, 3 flagged, 4 kept with the host's  */
+/* values (set by the caller between bbgr_jsonl_scan and bbgr_jsonl_offsets:   */
+/* the per-line columns hold the values, sizes[l] = {user, item, text, 0}      */
+/* bytes and spos[l] = their positions in `side`).                             */
+typedef struct {
+  int64_t n_bytes;           /* the chunk's bytes, < 2^31 - 1 */
+  const uint8_t *data;       /* DEVICE [n_bytes] */
+  int64_t n_lines;           /* HOST copy of bbgr_jsonl_count's totals[0] */
+  int32_t *line_end;         /* DEVICE [n_lines]: the line's terminator (n_bytes without one) */
+  const uint8_t *item_key;   /* DEVICE [item_key_len]: the item id's key */
+  int32_t item_key_len;      /* 1 .. 255 */
+  uint8_t *status;           /* [n_lines] */
+  float *rating;             /* [n_lines] per-line values of kept lines, 0 for others */
+  int32_t *helpful_vote;     /* [n_lines] */
+  uint8_t *verified;         /* [n_lines] */
+  int64_t *timestamp;        /* [n_lines] */
+  uint8_t *ts_valid;         /* [n_lines] */
+  int32_t *sizes;            /* [n_lines, 4] unescaped bytes of user id, item id, title, text */
+  int32_t *spos;             /* [n_lines, 4] their opening quotes in data, -1: null or missing */
+  int64_t *totals;           /* DEVICE int64 [4] */
+  int64_t *offs;             /* DEVICE int64 [4, n_lines + 1] (bbgr_jsonl_offsets) */
+  const uint8_t *side;       /* DEVICE [side_bytes]: the bytes of status-4 lines (nullable) */
+  int64_t side_bytes;
+  int64_t n_records;         /* HOST copies of offs[0 .. 3][n_lines] */
+  int64_t user_bytes, item_bytes, text_bytes;
+  float *out_rating;         /* [n_records] the compact columns, file order */
+  int32_t *out_helpful;
+  uint8_t *out_verified;
+  int64_t *out_timestamp;
+  uint8_t *out_ts_valid;
+  uint8_t *user_data;        /* [user_bytes] the records' user ids back to back */
+  int64_t *user_off;         /* [n_records] where record r's begins (the caller appends the total) */
+  uint8_t *item_data;        /* [item_bytes] */
+  int64_t *item_off;
+  uint8_t *text_data;        /* [text_bytes] title + " " + text per record */
+  int64_t *text_off;
+} bbgr_jsonl_args;
+/* totals[0] = the number of lines of data[0, n_bytes); totals[1 .. 3] = 0.    */
+/* One wave per 4096 bytes, a ballot of the terminators per 64-byte step. One  */
+/* memset and one launch on `stream`; reads n_bytes, data, totals.             */
+int bbgr_jsonl_count(const bbgr_jsonl_args *args, bbgr_stream_t stream);
+/* line_end[0 .. n_lines): the tiles' counts, their exclusive scan, and each   */
+/* terminator written at its rank (a rank outside [0, n_lines) is dropped).    */
+/* The workspace holds 8 bytes per 4096 of data and the scan's own. Size query */
+/* with workspace == NULL.                                                     */
+int bbgr_jsonl_lines(const bbgr_jsonl_args *args, void *workspace, size_t *workspace_bytes,
+                     bbgr_stream_t stream);
+/* status, the per-line values, sizes and spos of every line, one wave per     */
+/* line in 64-byte steps; totals = {blank, skipped, kept, flagged} lines.      */
+/* line_end is clamped into [0, n_bytes]. One memset and one launch.           */
+int bbgr_jsonl_scan(const bbgr_jsonl_args *args, bbgr_stream_t stream);
+/* offs[w][l] = the exclusive sum over the lines before l of: w = 0 kept lines */
+/* (status 2 or 4), w = 1 / 2 their user / item id bytes, w = 3 their text     */
+/* bytes (title + 1 + text; for status 4 sizes[l][2]); offs[w][n_lines] the    */
+/* totals, which the caller reads to size the outputs. Four scans. Size query  */
+/* with workspace == NULL.                                                     */
+int bbgr_jsonl_offsets(const bbgr_jsonl_args *args, void *workspace, size_t *workspace_bytes,
+                       bbgr_stream_t stream);
+/* The compact outputs of the kept lines: record offs[0][l] of line l gets the */
+/* line's values, its offsets, and its unescaped (status 2) or copied (status  */
+/* 4, from side) id and text bytes. Offsets read from offs are clamped into    */
+/* the outputs, positions in spos checked against the line and side_bytes. One */
+/* launch.                                                                     */
+int bbgr_jsonl_write(const bbgr_jsonl_args *args, bbgr_stream_t stream);
+
+/* The n strings data[offsets[r], offsets[r + 1]) (offsets clamped into        */
+/* [0, data_bytes]) numbered by first appearance: ids[r] (int32 [n]) the id of */
+/* record r's string, first_rec[k] (int32 [n], the first totals[0] entries     */
+/* written) the record where id k first appears, totals (DEVICE int64 [2]) =   */
+/* {distinct strings, collisions}. A 64-bit hash per string (FNV-1a and a      */
+/* finaliser, and-ed with hash_mask; 0: all 64 bits), a stable radix sort of   */
+/* (hash, record), per sorted slot a comparison of bytes and length with the   */
+/* left neighbour's where the hashes are equal (an unequal pair adds to        */
+/* collisions: with collisions != 0 the numbering is not vouched for and the   */
+/* caller numbers on the host), run heads, a scan of the heads in record       */
+/* order. The workspace holds 44 bytes per record and the sort's own. Size     */
+/* query with workspace == NULL; stream-ordered.                               */
+int bbgr_ids_number(int64_t n, const uint8_t *data, const int64_t *offsets, int64_t data_bytes,
+                    uint64_t hash_mask, int32_t *ids, int32_t *first_rec, int64_t *totals,
+                    void *workspace, size_t *workspace_bytes, bbgr_stream_t stream);
+/* The id table of bbgr_ids_number's first_rec. With tab_data == NULL:         */
+/* tab_offsets (DEVICE int64 [n_ids + 1]) = the exclusive sum of the strings'  */
+/* lengths, tab_offsets[n_ids] the table's bytes. With tab_data [tab_bytes]:   */
+/* string k copied to tab_offsets[k] (clamped; a first_rec outside [0, n) is   */
+/* skipped). Size query with workspace == NULL.                                */
+int bbgr_ids_table(int64_t n_ids, const int32_t *first_rec, int64_t n, const uint8_t *data,
+                   const int64_t *offsets, int64_t data_bytes, int64_t *tab_offsets,
+                   uint8_t *tab_data, int64_t tab_bytes, void *workspace, size_t *workspace_bytes,
+                   bbgr_stream_t stream);
+
+/* ------------------------------------------------------------------------- */
 /* Blueprint names (SURVEY §8(b)'s ABI sketch), thin forms of the above.      */
 /* ------------------------------------------------------------------------- */
 /* Y = diag(row_scale) A diag(col_scale) X (either scale NULL = ones), one    */
