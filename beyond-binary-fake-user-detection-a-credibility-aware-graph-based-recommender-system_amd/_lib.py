@@ -547,3 +547,34 @@ def workspace_query(fn_name: str, *args_before_ws, args_after=()) -> int:
     n = c_size_t(0)
     call(fn_name, *args_before_ws, None, ctypes.byref(n), *args_after)
     return n.value
+
+
+class Workspace:
+    """A device buffer that `call_with_workspace(..., keep=this)` reuses between
+    calls. The first call sizes it with a query. `grow=True` asks again on every
+    call and takes a larger buffer when the entry wants one (sizes that change
+    from call to call); `grow=False` asks once (a size fixed by arguments that
+    stay the same) and never again."""
+    __slots__ = ("buf", "grow")
+
+    def __init__(self, grow: bool = True):
+        self.buf = None
+        self.grow = grow
+
+
+def call_with_workspace(fn_name: str, *args_before_ws, after=None, device=None,
+                        keep: Workspace | None = None) -> torch.Tensor:
+    """The workspace protocol of include/bbgr.h from the caller's side: query
+    the size (workspace=NULL), take max(bytes, 1) of uint8 on `device` (or the
+    buffer `keep` holds), call, and return the buffer. `after`: the arguments
+    behind `workspace_bytes` (default: torch's current stream)."""
+    after = (stream_handle(),) if after is None else tuple(after)
+    buf = None if keep is None else keep.buf
+    if buf is None or keep.grow:
+        need = workspace_query(fn_name, *args_before_ws, args_after=after)
+        if buf is None or buf.numel() < need:
+            buf = torch.empty(max(need, 1), dtype=torch.uint8, device=device or "cuda")
+            if keep is not None:
+                keep.buf = buf
+    call(fn_name, *args_before_ws, buf.data_ptr(), ctypes.byref(c_size_t(buf.numel())), *after)
+    return buf

@@ -30,7 +30,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib
-from ._lib import call, ptr, stream_handle
+from ._lib import ptr
 from .graph import Csr
 from .propagate import Product, spmm
 
@@ -81,10 +81,7 @@ class EdgeSet:
             args = (ctypes.byref(cs), ptr(self.by_dst.perm), ptr(self.dst), ptr(w_in), ptr(attr), lda,
                     col_verified, col_align, float(beta), float(gamma), float(eps), ptr(w_raw),
                     ptr(w_edge), ptr(w_csr))
-            n = ctypes.c_size_t(0)
-            call("bbgr_ewa_normalize", *args, None, ctypes.byref(n), stream_handle())
-            ws = torch.empty(max(n.value, 1), dtype=torch.uint8, device=self.device)
-            call("bbgr_ewa_normalize", *args, ptr(ws), ctypes.byref(n), stream_handle())
+            _lib.call_with_workspace("bbgr_ewa_normalize", *args, device=self.device)
         return w_raw[:E], w_edge[:E], w_csr[:E]
 
     def src_order(self, w_edge: torch.Tensor) -> torch.Tensor:

@@ -79,13 +79,8 @@ class _RefCsr:
         self.indptr = torch.empty(self.n_rows + 1, dtype=torch.int32, device=dev)
         self.eid = torch.empty(max(E, 1), dtype=torch.int32, device=dev)
         cols = torch.arange(E, dtype=torch.int32, device=dev)
-        st = stream_handle()
-        args = (E, ptr(rows32), ptr(cols), self.n_rows, max(E, 1), ptr(self.indptr),
-                ptr(self.eid), None)
-        nb = _lib.workspace_query("bbgr_csr_build", *args, args_after=(st,))
-        ws = torch.empty(max(nb, 1), dtype=torch.uint8, device=dev)
-        have = ctypes.c_size_t(nb)
-        call("bbgr_csr_build", *args, ptr(ws), ctypes.byref(have), st)
+        _lib.call_with_workspace("bbgr_csr_build", E, ptr(rows32), ptr(cols), self.n_rows,
+                                 max(E, 1), ptr(self.indptr), ptr(self.eid), None, device=dev)
         self.nbr = (nbr32[self.eid[:E].long()].contiguous() if E
                     else torch.zeros(1, dtype=torch.int32, device=dev))
 
@@ -204,14 +199,10 @@ class SlasGraph:
             call("bbgr_mark_rows", exclude.numel(), ptr(exclude), 0, ptr(mask), n_rows, st)
         out = torch.empty(max(min(n, n_rows), 1), dtype=torch.int64, device=self.device)
         count = self._counts[slot:slot + 1]
-        if n_rows not in self._list_ws:
-            nb = _lib.workspace_query("bbgr_mask_to_list", n_rows, ptr(mask), ptr(out), ptr(count),
-                                      args_after=(st,))
-            self._list_ws[n_rows] = torch.empty(max(nb, 1), dtype=torch.uint8, device=self.device)
-        ws = self._list_ws[n_rows]
-        have = ctypes.c_size_t(ws.numel())
-        call("bbgr_mask_to_list", n_rows, ptr(mask), ptr(out), ptr(count), ptr(ws),
-             ctypes.byref(have), st)
+        # hipcub's temp size depends on n_rows only: one buffer per n_rows, sized once
+        keep = self._list_ws.setdefault(n_rows, _lib.Workspace(grow=False))
+        _lib.call_with_workspace("bbgr_mask_to_list", n_rows, ptr(mask), ptr(out), ptr(count),
+                                 after=(st,), device=self.device, keep=keep)
         call("bbgr_mark_ids32", n, ptr(ids32), 0, ptr(mask), n_rows, st)
         return out[: int(count.item())]
 
@@ -228,16 +219,15 @@ class SlasGraph:
         count = self._counts[2:3]
         a.count = ptr(count)
         st = stream_handle()
-        nb = ctypes.c_size_t(0)
-        call("bbgr_slas_induce", ctypes.byref(a), None, ctypes.byref(nb), st)
-        ws = torch.empty(max(nb.value, 1), dtype=torch.uint8, device=self.device)
-        call("bbgr_slas_induce", ctypes.byref(a), ptr(ws), ctypes.byref(nb), st)
+        keep = _lib.Workspace(grow=False)   # the count and the fill share one buffer
+        _lib.call_with_workspace("bbgr_slas_induce", ctypes.byref(a), after=(st,),
+                                 device=self.device, keep=keep)
         n_e = int(count.item())
         edges = torch.empty(2, n_e, dtype=torch.int64, device=self.device)
         eid = torch.empty(n_e, dtype=torch.int64, device=self.device)
         if n_e:
             a.out_edges, a.out_eid, a.capacity = ptr(edges), ptr(eid), n_e
-            call("bbgr_slas_induce", ctypes.byref(a), ptr(ws), ctypes.byref(nb), st)
+            _lib.call_with_workspace("bbgr_slas_induce", ctypes.byref(a), after=(st,), keep=keep)
         return edges, eid
 
     # -- build_slas_subgraph -------------------------------------------------------

@@ -66,10 +66,34 @@ inline bool ld_ok(const void *p, long ld, int d) {
 // Round a workspace carve offset up to 256 bytes.
 inline size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
 
-// The workspace protocol of an entry point `fn` that needs `need` bytes: a
-// null workspace asks for the size (*query, answered in *workspace_bytes), one
-// of fewer bytes is refused.
-inline int feat_workspace(const char *fn, size_t need, void *workspace, size_t *workspace_bytes,
+// The carve of a workspace: take(bytes) returns the offset of the next piece
+// and moves on by align_up(bytes). An entry point runs the same takes for a
+// size query and for a run, so `used` (the size it reports) and the offsets
+// it reads cannot disagree.
+struct Carver {
+  size_t used = 0;
+  size_t take(size_t bytes) {
+    const size_t at = used;
+    used += align_up(bytes);
+    return at;
+  }
+  template <typename T> size_t take_n(size_t count) { return take(sizeof(T) * count); }
+};
+
+// The piece of `workspace` at a Carver offset, as T *.
+template <typename T> inline T *ws_at(void *workspace, size_t off) {
+  return reinterpret_cast<T *>(static_cast<char *>(workspace) + off);
+}
+template <typename T> inline const T *ws_at(const void *workspace, size_t off) {
+  return reinterpret_cast<const T *>(static_cast<const char *>(workspace) + off);
+}
+
+// The workspace protocol of every entry point that takes (workspace,
+// workspace_bytes): `fn` (the exported name the caller used) needs `need`
+// bytes; a null workspace asks for the size (*query, answered in
+// *workspace_bytes), one of fewer bytes is refused. The only place that reads
+// or writes *workspace_bytes, and the only refusal text.
+inline int take_workspace(const char *fn, size_t need, void *workspace, size_t *workspace_bytes,
                           bool *query) {
   BBGR_REQUIRE_IN(fn, workspace_bytes, "null workspace_bytes");
   *query = workspace == nullptr;

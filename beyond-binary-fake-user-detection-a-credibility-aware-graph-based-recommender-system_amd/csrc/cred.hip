@@ -153,20 +153,14 @@ extern "C" int bbgr_ewa_normalize(const bbgr_csr *csr, const int32_t *perm, cons
   const long E = csr->nnz;
   // raw weights in input order are needed for w_edge by the coalesced pass
   const bool own_raw = !w_in && !w_raw;
-  const size_t a_raw = own_raw ? align_up(4 * (size_t)(E > 0 ? E : 1)) : 0;
-  const size_t a_csr = align_up(4 * (size_t)(E > 0 ? E : 1));
-  const size_t a_den = align_up(4 * (size_t)(csr->n_rows > 0 ? csr->n_rows : 1));
-  const size_t need = a_raw + a_csr + a_den +
-                      align_up(4 * (size_t)(csr->n_chunks > 0 ? csr->n_chunks : 1));
-  if (!workspace) {
-    *workspace_bytes = need;
-    return BBGR_OK;
-  }
-  if (*workspace_bytes < need) {
-    set_error("bbgr_ewa_normalize: workspace %zu < %zu bytes", *workspace_bytes, need);
-    return BBGR_ERR_WORKSPACE;
-  }
-  if (csr->n_rows == 0 || E == 0) return BBGR_OK;
+  Carver C;
+  const size_t off_raw = own_raw ? C.take_n<float>((size_t)(E > 0 ? E : 1)) : 0;
+  const size_t off_csr = C.take_n<float>((size_t)(E > 0 ? E : 1));
+  const size_t off_den = C.take_n<float>((size_t)(csr->n_rows > 0 ? csr->n_rows : 1));
+  const size_t off_part = C.take_n<float>((size_t)(csr->n_chunks > 0 ? csr->n_chunks : 1));
+  bool query;
+  const int rc = take_workspace("bbgr_ewa_normalize", C.used, workspace, workspace_bytes, &query);
+  if (rc || query || csr->n_rows == 0 || E == 0) return rc;
   BBGR_REQUIRE(csr->indptr && perm, "bbgr_ewa_normalize: null indptr / perm");
   BBGR_REQUIRE(csr->n_chunks == 0 || (csr->chunks && csr->long_threshold > 0),
                "bbgr_ewa_normalize: csr needs its load-balance plan");
@@ -175,16 +169,15 @@ extern "C" int bbgr_ewa_normalize(const bbgr_csr *csr, const int32_t *perm, cons
                         col_verified < lda && col_align < lda),
                "bbgr_ewa_normalize: need w_in or edge_attr with valid columns");
   hipStream_t st = as_stream(stream);
-  char *ws = static_cast<char *>(workspace);
   const float *raw = w_in;
   if (!w_in) {
-    float *out = own_raw ? reinterpret_cast<float *>(ws) : w_raw;
+    float *out = own_raw ? ws_at<float>(workspace, off_raw) : w_raw;
     hipLaunchKernelGGL(ewa_raw_kernel, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, st, E,
                        edge_attr, (long)lda, col_verified, col_align, beta, gamma, out);
     BBGR_LAUNCHED("ewa_raw_kernel");
     raw = out;
   }
-  float *raw_csr = reinterpret_cast<float *>(ws + a_raw);
+  float *raw_csr = ws_at<float>(workspace, off_csr);
   hipLaunchKernelGGL(raw_csr_kernel, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, st, E,
                      perm, raw, raw_csr);
   BBGR_LAUNCHED("raw_csr_kernel");
@@ -198,8 +191,8 @@ extern "C" int bbgr_ewa_normalize(const bbgr_csr *csr, const int32_t *perm, cons
   P.perm = perm;
   P.raw = raw;
   P.raw_csr = raw_csr;
-  P.denom = reinterpret_cast<float *>(ws + a_raw + a_csr);
-  P.partial = reinterpret_cast<float *>(ws + a_raw + a_csr + a_den);
+  P.denom = ws_at<float>(workspace, off_den);
+  P.partial = ws_at<float>(workspace, off_part);
   P.eps = eps;
   P.w_edge = dst ? nullptr : w_edge;
   P.w_csr = w_csr;

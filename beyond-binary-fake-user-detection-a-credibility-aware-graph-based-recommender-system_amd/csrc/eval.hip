@@ -613,23 +613,18 @@ struct EvalLayout {
 static EvalLayout eval_layout(const bbgr_eval_args *a, bool full, int cus) {
   EvalLayout L{};
   L.n_chunks = (a->n_users + EVAL_CHUNK - 1) / EVAL_CHUNK;
-  size_t off = 0;
-  L.covered = off;
-  off = align_up(off + (size_t)a->n_k * a->n_items);
-  L.partial = off;
-  off = align_up(off + sizeof(double) * (size_t)a->n_k * (L.n_chunks > 0 ? L.n_chunks : 1) *
-                           EVAL_NTERM);
+  Carver C;
+  L.covered = C.take((size_t)a->n_k * a->n_items);
+  L.partial = C.take_n<double>((size_t)a->n_k * (L.n_chunks > 0 ? L.n_chunks : 1) * EVAL_NTERM);
   if (full) {
     L.batch = a->n_users < FULL_BATCH ? a->n_users : FULL_BATCH;
     L.splits = full_splits(L.batch, a->n_items, cus, FULL_USERS);
     L.km = full_km(a->k_max);
     const size_t n = (size_t)(L.batch > 0 ? L.batch : 1) * L.splits * 2 * L.km;
-    L.lscore = off;
-    off = align_up(off + sizeof(float) * n);
-    L.litem = off;
-    off = align_up(off + sizeof(int) * n);
+    L.lscore = C.take_n<float>(n);
+    L.litem = C.take_n<int>(n);
   }
-  L.total = off;
+  L.total = C.used;
   return L;
 }
 
@@ -676,9 +671,9 @@ static int launch_terms(const bbgr_eval_args *a, bool full, const EvalLayout &L,
   S.item_pop = a->item_pop;
   S.self_info_denom = a->self_info_denom;
   S.group = a->group;
-  S.covered = reinterpret_cast<unsigned char *>(ws + L.covered);
+  S.covered = ws_at<unsigned char>(ws, L.covered);
   S.n_items = a->n_items;
-  S.partial = reinterpret_cast<double *>(ws + L.partial);
+  S.partial = ws_at<double>(ws, L.partial);
   S.n_chunks = L.n_chunks;
   BBGR_HIP(hipMemsetAsync(S.covered, 0, (size_t)a->n_k * a->n_items, st));
   if (L.n_chunks > 0) {
@@ -881,16 +876,11 @@ extern "C" int bbgr_eval_sampled(const bbgr_eval_args *a, void *workspace,
   if (int rc = check_common(a, "bbgr_eval_sampled")) return rc;
   BBGR_REQUIRE(a->n_neg >= 0 && 1 + a->n_neg <= EVAL_MAX_CAND && a->k_max <= EVAL_MAX_K,
                "bbgr_eval_sampled: 1+n_neg <= 256, k_max <= 64");
-  BBGR_REQUIRE(workspace_bytes, "bbgr_eval_sampled: null workspace_bytes");
   const EvalLayout L = eval_layout(a, false, 0);
-  if (!workspace) {
-    *workspace_bytes = L.total;
-    return BBGR_OK;
-  }
-  if (*workspace_bytes < L.total) {
-    set_error("bbgr_eval_sampled: workspace %zu < %zu bytes", *workspace_bytes, L.total);
-    return BBGR_ERR_WORKSPACE;
-  }
+  bool query;
+  if (int rc = take_workspace("bbgr_eval_sampled", L.total, workspace, workspace_bytes, &query))
+    return rc;
+  if (query) return BBGR_OK;
   const int d = a->d;
   if (d != 64 && d != 128 && d != 256) return unsupported_width("bbgr_eval_sampled", d, true);
   hipStream_t st = as_stream(stream);
@@ -941,14 +931,10 @@ extern "C" int bbgr_eval_full(const bbgr_eval_args *a, void *workspace, size_t *
     return BBGR_ERR_UNSUPPORTED;
   }
   const EvalLayout L = eval_layout(a, true, device_cus());
-  if (!workspace) {
-    *workspace_bytes = L.total;
-    return BBGR_OK;
-  }
-  if (*workspace_bytes < L.total) {
-    set_error("bbgr_eval_full: workspace %zu < %zu bytes", *workspace_bytes, L.total);
-    return BBGR_ERR_WORKSPACE;
-  }
+  bool query;
+  if (int rc = take_workspace("bbgr_eval_full", L.total, workspace, workspace_bytes, &query))
+    return rc;
+  if (query) return BBGR_OK;
   hipStream_t st = as_stream(stream);
   char *ws = static_cast<char *>(workspace);
   for (long b0 = 0; b0 < a->n_users; b0 += L.batch) {
@@ -965,8 +951,8 @@ extern "C" int bbgr_eval_full(const bbgr_eval_args *a, void *workspace, size_t *
     P.n_splits = (int)L.splits;
     const long per = (a->n_items + L.splits - 1) / L.splits;
     P.split_items = (int)((per + FULL_TILE - 1) / FULL_TILE * FULL_TILE);
-    P.list_score = reinterpret_cast<float *>(ws + L.lscore);
-    P.list_item = reinterpret_cast<int *>(ws + L.litem);
+    P.list_score = ws_at<float>(ws, L.lscore);
+    P.list_item = ws_at<int>(ws, L.litem);
     int rc;
     switch (d * 100 + L.km) {
       case 6416: rc = launch_full<64, 16>(P, st); break;
@@ -1001,15 +987,10 @@ extern "C" int bbgr_eval_lists(const bbgr_eval_args *a, void *workspace, size_t 
   BBGR_REQUIRE(a->n_users == 0 || (a->users && a->te_indptr && a->te_indices && a->topk &&
                                    a->item_pop && a->sums),
                "bbgr_eval_lists: null array (users, te_indptr, te_indices, topk, item_pop, sums)");
-  BBGR_REQUIRE(workspace_bytes, "bbgr_eval_lists: null workspace_bytes");
   const EvalLayout L = eval_layout(a, false, 0);
-  if (!workspace) {
-    *workspace_bytes = L.total;
-    return BBGR_OK;
-  }
-  if (*workspace_bytes < L.total) {
-    set_error("bbgr_eval_lists: workspace %zu < %zu bytes", *workspace_bytes, L.total);
-    return BBGR_ERR_WORKSPACE;
-  }
+  bool query;
+  if (int rc = take_workspace("bbgr_eval_lists", L.total, workspace, workspace_bytes, &query))
+    return rc;
+  if (query) return BBGR_OK;
   return launch_terms(a, true, L, static_cast<char *>(workspace), as_stream(stream));
 }

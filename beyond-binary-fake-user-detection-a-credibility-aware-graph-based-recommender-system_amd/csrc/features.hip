@@ -287,7 +287,7 @@ extern "C" int bbgr_feat_items(const bbgr_feat_columns *c, const int32_t *i_indp
   int rc = feat_columns_ok(fn, c);
   if (rc) return rc;
   bool query;
-  rc = feat_workspace(fn, feat_long_bytes((long)c->n), workspace, workspace_bytes, &query);
+  rc = take_workspace(fn, feat_long_bytes((long)c->n), workspace, workspace_bytes, &query);
   if (rc || query) return rc;
   if (c->n_items == 0) return BBGR_OK;
   BBGR_REQUIRE(i_indptr, "bbgr_feat_items: null i_indptr");
@@ -306,9 +306,10 @@ extern "C" int bbgr_feat_users(const bbgr_feat_columns *c, const bbgr_feat_user_
   BBGR_REQUIRE(a, "bbgr_feat_users: null args");
   bool query;
   // the long-row list, then the packed records
-  const size_t off_packed = feat_long_bytes((long)c->n);
-  rc = feat_workspace(fn, off_packed + align_up(sizeof(int4) * (size_t)c->n), workspace,
-                      workspace_bytes, &query);
+  Carver C;
+  C.take(feat_long_bytes((long)c->n));
+  const size_t off_packed = C.take_n<int4>((size_t)c->n);
+  rc = take_workspace(fn, C.used, workspace, workspace_bytes, &query);
   if (rc || query) return rc;
   if (c->n_users == 0) return BBGR_OK;
   BBGR_REQUIRE(a->u_indptr, "bbgr_feat_users: null u_indptr");
@@ -323,7 +324,7 @@ extern "C" int bbgr_feat_users(const bbgr_feat_columns *c, const bbgr_feat_user_
   BBGR_REQUIRE(a->total_reviews, "bbgr_feat_users: null total_reviews");
   BBGR_REQUIRE(a->helpful_reviews, "bbgr_feat_users: null helpful_reviews");
   hipStream_t st = as_stream(stream);
-  int4 *packed = reinterpret_cast<int4 *>(static_cast<char *>(workspace) + off_packed);
+  int4 *packed = ws_at<int4>(workspace, off_packed);
   if ((rc = feat_pack<false>(c, packed, st))) return rc;
   return feat_row_pass(fn, UsersPass{{a->u_indptr}, *c, *a, packed}, c->n_users, (long)c->n,
                        workspace, st);

@@ -34,11 +34,10 @@
 // No fast-math flag on this file: the divisions above must be IEEE double.
 //
 // Measured in DESIGN 4g (tools/features_bench.py, tools/text_bench.py).
-#include "common.h"
+#include "cub_temp.h"
 #include "features.h"
 #include "text.h"
 
-#include <hipcub/hipcub.hpp>
 
 namespace bbgr {
 
@@ -337,20 +336,16 @@ static int text_unique_pooled(const char *fn, const bbgr_text_args *a, int64_t t
   int group_bits = 1;
   while (group_bits < 32 && (unsigned)n_groups >> group_bits) ++group_bits;
   if (T > 0) {
-    (void)hipcub::DeviceRadixSort::SortPairs(
-        nullptr, t_hash, (const unsigned long long *)nullptr, (unsigned long long *)nullptr,
-        (const uint32_t *)nullptr, (uint32_t *)nullptr, T, 0, 64, (hipStream_t) nullptr);
-    (void)hipcub::DeviceRadixSort::SortPairs(nullptr, t_group, (const uint32_t *)nullptr,
-                                             (uint32_t *)nullptr, (const uint32_t *)nullptr,
-                                             (uint32_t *)nullptr, T, 0, group_bits,
-                                             (hipStream_t) nullptr);
+    t_hash = hcub::sort_pairs_temp<unsigned long long, uint32_t>(T, 0, 64);
+    t_group = hcub::sort_pairs_temp<uint32_t, uint32_t>(T, 0, group_bits);
   }
   const size_t temp = t_hash > t_group ? t_hash : t_group;
-  const size_t off_g1 = align_up(base);
-  const size_t off_g2 = off_g1 + align_up(sizeof(uint32_t) * nt);
-  const size_t off_tmp = off_g2 + align_up(sizeof(uint32_t) * nt);
+  Carver C;
+  C.take(base);
+  const size_t off_g1 = C.take_n<uint32_t>(nt), off_g2 = C.take_n<uint32_t>(nt);
+  const size_t off_tmp = C.take(temp);
   bool query;
-  int rc = feat_workspace(fn, off_tmp + align_up(temp), workspace, workspace_bytes, &query);
+  int rc = take_workspace(fn, C.used, workspace, workspace_bytes, &query);
   if (rc || query) return rc;
   hipStream_t st = as_stream(stream);
   if (T > 0 && n > 0 && (stages & BBGR_TEXT_STAGE_EMIT)) {
@@ -358,29 +353,24 @@ static int text_unique_pooled(const char *fn, const bbgr_text_args *a, int64_t t
     rc = bbgr_text_unique_stages(a, total_tokens, BBGR_TEXT_STAGE_EMIT, workspace, &nb, stream);
     if (rc) return rc;
   }
-  char *ws = static_cast<char *>(workspace);
   const TextWorkspace W = text_workspace(n, nt);
-  unsigned long long *k1 = reinterpret_cast<unsigned long long *>(ws + W.off_k1);
-  unsigned long long *k2 = reinterpret_cast<unsigned long long *>(ws + W.off_k2);
-  uint32_t *v1 = reinterpret_cast<uint32_t *>(ws + W.off_v1);
-  uint32_t *v2 = reinterpret_cast<uint32_t *>(ws + W.off_v2);
-  uint32_t *g1 = reinterpret_cast<uint32_t *>(ws + off_g1);
-  uint32_t *g2 = reinterpret_cast<uint32_t *>(ws + off_g2);
-  void *tmp = ws + off_tmp;
+  unsigned long long *k1 = ws_at<unsigned long long>(workspace, W.off_k1);
+  unsigned long long *k2 = ws_at<unsigned long long>(workspace, W.off_k2);
+  uint32_t *v1 = ws_at<uint32_t>(workspace, W.off_v1), *v2 = ws_at<uint32_t>(workspace, W.off_v2);
+  uint32_t *g1 = ws_at<uint32_t>(workspace, off_g1), *g2 = ws_at<uint32_t>(workspace, off_g2);
+  void *tmp = ws_at<char>(workspace, off_tmp);
   const TextTokens K = text_tokens(a, workspace, W, T);
   const unsigned tok_blocks = (unsigned)(((long)T + 255) / 256);
   if (T > 0 && n > 0 && (stages & BBGR_TEXT_STAGE_SORT)) {
     // by hash, then (stable) by group: equal (group, hash) pairs end side by
     // side, in text order. v1 (the identity before) takes the final order.
-    size_t tb = temp;
-    BBGR_HIP(hipcub::DeviceRadixSort::SortPairs(tmp, tb, (const unsigned long long *)k1, k2,
-                                                (const uint32_t *)v1, v2, T, 0, 64, st));
+    BBGR_HIP(hcub::sort_pairs(tmp, temp, (const unsigned long long *)k1, k2, (const uint32_t *)v1,
+                              v2, T, 0, 64, st));
     hipLaunchKernelGGL(pool_keys_kernel, dim3(tok_blocks), dim3(256), 0, st, K,
                        (const uint32_t *)v2, group, n_groups, g1);
     BBGR_LAUNCHED("pool_keys_kernel");
-    tb = temp;
-    BBGR_HIP(hipcub::DeviceRadixSort::SortPairs(tmp, tb, (const uint32_t *)g1, g2,
-                                                (const uint32_t *)v2, v1, T, 0, group_bits, st));
+    BBGR_HIP(hcub::sort_pairs(tmp, temp, (const uint32_t *)g1, g2, (const uint32_t *)v2, v1, T, 0,
+                              group_bits, st));
   }
   if (!(stages & BBGR_TEXT_STAGE_VERIFY)) return BBGR_OK;
   if (n_groups > 0) {
@@ -431,7 +421,7 @@ extern "C" int bbgr_feat_lenlog(const bbgr_feat_columns *c, double *lenlog_sum, 
   static const char *fn = "bbgr_feat_lenlog";
   if (int rc = feat_columns_ok(fn, c)) return rc;
   bool query;
-  int rc = feat_workspace(fn, align_up(sizeof(double) * LENLOG_GRID), workspace, workspace_bytes,
+  int rc = take_workspace(fn, align_up(sizeof(double) * LENLOG_GRID), workspace, workspace_bytes,
                           &query);
   if (rc || query) return rc;
   BBGR_REQUIRE_IN(fn, lenlog_sum, "null lenlog_sum");
@@ -452,7 +442,7 @@ extern "C" int bbgr_feat_item_means(const bbgr_feat_columns *c, const int32_t *i
   static const char *fn = "bbgr_feat_item_means";
   if (int rc = feat_columns_ok(fn, c)) return rc;
   bool query;
-  int rc = feat_workspace(fn, feat_long_bytes((long)c->n), workspace, workspace_bytes, &query);
+  int rc = take_workspace(fn, feat_long_bytes((long)c->n), workspace, workspace_bytes, &query);
   if (rc || query) return rc;
   if (c->n_items == 0) return BBGR_OK;
   BBGR_REQUIRE_IN(fn, i_indptr, "null i_indptr");
@@ -472,24 +462,22 @@ extern "C" int bbgr_feat_gaps(const bbgr_feat_columns *c, const int32_t *u_indpt
   if (n > 0) {
     const hipcub::CountingInputIterator<int> row(0);
     const RowIter seg_b(row, RowBound{nullptr, n, false}), seg_e(row, RowBound{nullptr, n, true});
-    (void)hipcub::DeviceSegmentedRadixSort::SortKeys(nullptr, t_sort, (const double *)nullptr,
-                                                     (double *)nullptr, n, U, seg_b, seg_e, 0, 64,
-                                                     (hipStream_t) nullptr);
+    t_sort = hcub::seg_sort_keys_temp<double>(n, U, seg_b, seg_e, 0, 64);
   }
-  const size_t off_d1 = feat_long_bytes((long)n, GAP_SHORT_ROW);
-  const size_t off_d2 = off_d1 + align_up(sizeof(double) * (size_t)n);
-  const size_t off_tmp = off_d2 + align_up(sizeof(double) * (size_t)n);
+  // the long-row list, the day keys before and after the sort, the sort's temp
+  Carver C;
+  C.take(feat_long_bytes((long)n, GAP_SHORT_ROW));
+  const size_t off_d1 = C.take_n<double>((size_t)n), off_d2 = C.take_n<double>((size_t)n);
+  const size_t off_tmp = C.take(t_sort);
   bool query;
-  int rc = feat_workspace(fn, off_tmp + align_up(t_sort), workspace, workspace_bytes, &query);
+  int rc = take_workspace(fn, C.used, workspace, workspace_bytes, &query);
   if (rc || query) return rc;
   if (U == 0) return BBGR_OK;
   BBGR_REQUIRE_IN(fn, u_indptr, "null u_indptr");
   BBGR_REQUIRE_IN(fn, n == 0 || u_eid, "null u_eid");
   BBGR_REQUIRE_IN(fn, etg, "null etg");
   hipStream_t st = as_stream(stream);
-  char *ws = static_cast<char *>(workspace);
-  double *d1 = reinterpret_cast<double *>(ws + off_d1);
-  double *d2 = reinterpret_cast<double *>(ws + off_d2);
+  double *d1 = ws_at<double>(workspace, off_d1), *d2 = ws_at<double>(workspace, off_d2);
   const RowBound rb_of{u_indptr, n, false}, re_of{u_indptr, n, true};
   if (n > 0) {
     hipLaunchKernelGGL(feat2_days_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, *c,
@@ -497,9 +485,8 @@ extern "C" int bbgr_feat_gaps(const bbgr_feat_columns *c, const int32_t *u_indpt
     BBGR_LAUNCHED("feat2_days_kernel");
     const hipcub::CountingInputIterator<int> row(0);
     const RowIter seg_b(row, rb_of), seg_e(row, re_of);
-    size_t tb = t_sort;
-    BBGR_HIP(hipcub::DeviceSegmentedRadixSort::SortKeys(ws + off_tmp, tb, (const double *)d1, d2,
-                                                        n, U, seg_b, seg_e, 0, 64, st));
+    BBGR_HIP(hcub::seg_sort_keys(ws_at<char>(workspace, off_tmp), t_sort, (const double *)d1, d2,
+                                 n, U, seg_b, seg_e, 0, 64, st));
   }
   return feat_row_pass(fn, GapsPass{u_indptr, n, d2, etg}, U, (long)n, workspace, st);
 }
@@ -512,9 +499,10 @@ extern "C" int bbgr_feat_users_v2(const bbgr_feat_columns *c, const bbgr_feat_us
   BBGR_REQUIRE_IN(fn, a, "null args");
   bool query;
   // the long-row list, then the packed records
-  const size_t off_packed = feat_long_bytes((long)c->n);
-  int rc = feat_workspace(fn, off_packed + align_up(sizeof(int4) * (size_t)c->n), workspace,
-                          workspace_bytes, &query);
+  Carver C;
+  C.take(feat_long_bytes((long)c->n));
+  const size_t off_packed = C.take_n<int4>((size_t)c->n);
+  int rc = take_workspace(fn, C.used, workspace, workspace_bytes, &query);
   if (rc || query) return rc;
   if (c->n_users == 0) return BBGR_OK;
   BBGR_REQUIRE_IN(fn, a->u_indptr, "null u_indptr");
@@ -533,7 +521,7 @@ extern "C" int bbgr_feat_users_v2(const bbgr_feat_columns *c, const bbgr_feat_us
   BBGR_REQUIRE_IN(fn, a->helpful_reviews, "null helpful_reviews");
   BBGR_REQUIRE_IN(fn, a->user_extra, "null user_extra");
   hipStream_t st = as_stream(stream);
-  int4 *packed = reinterpret_cast<int4 *>(static_cast<char *>(workspace) + off_packed);
+  int4 *packed = ws_at<int4>(workspace, off_packed);
   if ((rc = feat_pack<true>(c, packed, st))) return rc;
   return feat_row_pass(fn, UsersV2Pass{{a->u_indptr}, *c, *a, packed}, c->n_users, (long)c->n,
                        workspace, st);

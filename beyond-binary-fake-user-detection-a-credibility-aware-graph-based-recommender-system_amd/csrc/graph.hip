@@ -10,9 +10,7 @@
 //   samplers              Version-2/lighgcn_cu_pop.py:330-376, lightgcn.py:296-300
 #include <stdarg.h>
 
-#include <hipcub/hipcub.hpp>
-
-#include "common.h"
+#include "cub_temp.h"
 
 namespace bbgr {
 
@@ -430,24 +428,19 @@ extern "C" int bbgr_csr_build(int64_t nnz, const int32_t *rows,
   hipStream_t st = as_stream(stream);
   const int end_bit = bits_for((uint64_t)(n_rows > 0 ? n_rows : 1) *
                                (uint64_t)(n_cols > 0 ? n_cols : 1));
-  size_t temp = 0;
-  BBGR_HIP(hipcub::DeviceRadixSort::SortPairs(
-      nullptr, temp, (unsigned long long *)nullptr, (unsigned long long *)nullptr,
-      (int *)nullptr, (int *)nullptr, (int)nnz, 0, end_bit, st));
-  const size_t off_k1 = 0;
-  const size_t off_k2 = align_up(off_k1 + 8 * (size_t)nnz);
-  const size_t off_i1 = align_up(off_k2 + 8 * (size_t)nnz);
-  const size_t off_i2 = align_up(off_i1 + 4 * (size_t)nnz);
-  const size_t off_t = align_up(off_i2 + 4 * (size_t)nnz);
-  const size_t need = align_up(off_t + temp);
-  if (!workspace) {
-    *workspace_bytes = need;
-    return BBGR_OK;
-  }
-  if (*workspace_bytes < need) {
-    set_error("bbgr_csr_build: workspace %zu < %zu", *workspace_bytes, need);
-    return BBGR_ERR_WORKSPACE;
-  }
+  hipError_t sizing;
+  const size_t temp =
+      hcub::sort_pairs_temp<unsigned long long, int>((int)nnz, 0, end_bit, &sizing);
+  BBGR_HIP(sizing);
+  Carver C;
+  const size_t off_k1 = C.take_n<unsigned long long>((size_t)nnz);
+  const size_t off_k2 = C.take_n<unsigned long long>((size_t)nnz);
+  const size_t off_i1 = C.take_n<int>((size_t)nnz);
+  const size_t off_i2 = C.take_n<int>((size_t)nnz);
+  const size_t off_t = C.take(temp);
+  bool query;
+  const int rc = take_workspace("bbgr_csr_build", C.used, workspace, workspace_bytes, &query);
+  if (rc || query) return rc;
   BBGR_REQUIRE(indptr, "bbgr_csr_build: null indptr");
   if (nnz == 0) {
     hipLaunchKernelGGL(fill_int_kernel, dim3(blocks_for((long)n_rows + 1)), dim3(256), 0,
@@ -456,16 +449,15 @@ extern "C" int bbgr_csr_build(int64_t nnz, const int32_t *rows,
     return BBGR_OK;
   }
   BBGR_REQUIRE(rows && cols && indices, "bbgr_csr_build: null arrays");
-  char *ws = (char *)workspace;
-  auto *k1 = (unsigned long long *)(ws + off_k1);
-  auto *k2 = (unsigned long long *)(ws + off_k2);
-  int *i1 = (int *)(ws + off_i1);
-  int *i2 = perm_out ? perm_out : (int *)(ws + off_i2);
+  auto *k1 = ws_at<unsigned long long>(workspace, off_k1);
+  auto *k2 = ws_at<unsigned long long>(workspace, off_k2);
+  int *i1 = ws_at<int>(workspace, off_i1);
+  int *i2 = perm_out ? perm_out : ws_at<int>(workspace, off_i2);
   hipLaunchKernelGGL(csr_keys_kernel, dim3(blocks_for(nnz)), dim3(256), 0, st,
                      (long)nnz, rows, cols, (long)n_cols, k1, i1);
   BBGR_LAUNCHED("csr_keys_kernel");
-  BBGR_HIP(hipcub::DeviceRadixSort::SortPairs(ws + off_t, temp, k1, k2, i1, i2,
-                                              (int)nnz, 0, end_bit, st));
+  BBGR_HIP(hcub::sort_pairs(ws_at<char>(workspace, off_t), temp, k1, k2, i1, i2, (int)nnz, 0,
+                            end_bit, st));
   hipLaunchKernelGGL(csr_split_kernel, dim3(blocks_for(nnz)), dim3(256), 0, st,
                      (long)nnz, k2, (unsigned long long)n_cols, n_rows, indptr,
                      indices);
@@ -483,51 +475,47 @@ static int plan_defaults(const bbgr_csr *csr, int *thr, int *chunk) {
   return BBGR_OK;
 }
 
-// Workspace: nch[n], ch_off[n], sflag[n], sp_off[n], cub temp.
-static int plan_scan(const bbgr_csr *csr, void *workspace, size_t *workspace_bytes,
-                     hipStream_t st, int **nch, int **ch_off, int **sflag,
-                     int **sp_off, bool *query) {
+// Workspace: nch[n + 1], ch_off[n + 1], sflag[n + 1], sp_off[n + 1], cub temp.
+// `who`: the entry point the caller called.
+static int plan_scan(const char *who, const bbgr_csr *csr, void *workspace,
+                     size_t *workspace_bytes, hipStream_t st, int **nch, int **ch_off,
+                     int **sflag, int **sp_off, bool *query) {
   const int n = csr->n_rows;
-  size_t temp = 0;
-  BBGR_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, temp, (int *)nullptr,
-                                            (int *)nullptr, n > 0 ? n : 1, st));
-  const size_t a = align_up(4 * (size_t)(n + 1));
-  const size_t need = 4 * a + align_up(temp);
-  *query = workspace == nullptr;
-  if (!workspace) {
-    *workspace_bytes = need;
-    return BBGR_OK;
-  }
-  if (*workspace_bytes < need) {
-    set_error("plan: workspace %zu < %zu", *workspace_bytes, need);
-    return BBGR_ERR_WORKSPACE;
-  }
+  hipError_t sizing;
+  const size_t temp = hcub::exclusive_sum_temp<int *, int *>(n > 0 ? n : 1, &sizing);
+  BBGR_HIP(sizing);
+  Carver C;
+  const size_t off_nch = C.take_n<int>((size_t)(n + 1)), off_ch = C.take_n<int>((size_t)(n + 1));
+  const size_t off_sf = C.take_n<int>((size_t)(n + 1)), off_sp = C.take_n<int>((size_t)(n + 1));
+  const size_t off_tmp = C.take(temp);
+  int rc = take_workspace(who, C.used, workspace, workspace_bytes, query);
+  if (rc || *query) return rc;
   int thr, chunk;
-  int rc = plan_defaults(csr, &thr, &chunk);
+  rc = plan_defaults(csr, &thr, &chunk);
   if (rc) return rc;
-  char *ws = (char *)workspace;
-  *nch = (int *)ws;
-  *ch_off = (int *)(ws + a);
-  *sflag = (int *)(ws + 2 * a);
-  *sp_off = (int *)(ws + 3 * a);
+  *nch = ws_at<int>(workspace, off_nch);
+  *ch_off = ws_at<int>(workspace, off_ch);
+  *sflag = ws_at<int>(workspace, off_sf);
+  *sp_off = ws_at<int>(workspace, off_sp);
+  void *tmp = ws_at<char>(workspace, off_tmp);
   if (n == 0) return BBGR_OK;
   hipLaunchKernelGGL(plan_counts_kernel, dim3(blocks_for(n)), dim3(256), 0, st, n,
                      csr->indptr, thr, chunk, *nch, *sflag);
   BBGR_LAUNCHED("plan_counts_kernel");
-  BBGR_HIP(hipcub::DeviceScan::ExclusiveSum(ws + 4 * a, temp, *nch, *ch_off, n, st));
-  BBGR_HIP(hipcub::DeviceScan::ExclusiveSum(ws + 4 * a, temp, *sflag, *sp_off, n, st));
+  BBGR_HIP(hcub::exclusive_sum(tmp, temp, *nch, *ch_off, n, st));
+  BBGR_HIP(hcub::exclusive_sum(tmp, temp, *sflag, *sp_off, n, st));
   return BBGR_OK;
 }
 
 extern "C" int bbgr_csr_plan_count(const bbgr_csr *csr, int32_t *n_chunks,
                                    int32_t *n_split, void *workspace,
                                    size_t *workspace_bytes, bbgr_stream_t stream) {
-  BBGR_REQUIRE(csr && workspace_bytes && csr->indptr, "bbgr_csr_plan_count: null arg");
+  BBGR_REQUIRE(csr && csr->indptr, "bbgr_csr_plan_count: null arg");
   hipStream_t st = as_stream(stream);
   int *nch, *ch_off, *sflag, *sp_off;
   bool query;
-  int rc = plan_scan(csr, workspace, workspace_bytes, st, &nch, &ch_off, &sflag,
-                     &sp_off, &query);
+  int rc = plan_scan("bbgr_csr_plan_count", csr, workspace, workspace_bytes, st, &nch, &ch_off,
+                     &sflag, &sp_off, &query);
   if (rc || query) return rc;
   BBGR_REQUIRE(n_chunks && n_split, "bbgr_csr_plan_count: null outputs");
   const int n = csr->n_rows;
@@ -550,12 +538,12 @@ extern "C" int bbgr_csr_plan_count(const bbgr_csr *csr, int32_t *n_chunks,
 extern "C" int bbgr_csr_plan_build(const bbgr_csr *csr, int32_t *chunks,
                                    int32_t *split, void *workspace,
                                    size_t *workspace_bytes, bbgr_stream_t stream) {
-  BBGR_REQUIRE(csr && workspace_bytes && csr->indptr, "bbgr_csr_plan_build: null arg");
+  BBGR_REQUIRE(csr && csr->indptr, "bbgr_csr_plan_build: null arg");
   hipStream_t st = as_stream(stream);
   int *nch, *ch_off, *sflag, *sp_off;
   bool query;
-  int rc = plan_scan(csr, workspace, workspace_bytes, st, &nch, &ch_off, &sflag,
-                     &sp_off, &query);
+  int rc = plan_scan("bbgr_csr_plan_build", csr, workspace, workspace_bytes, st, &nch, &ch_off,
+                     &sflag, &sp_off, &query);
   if (rc || query) return rc;
   const int n = csr->n_rows;
   if (n == 0) return BBGR_OK;
@@ -594,29 +582,25 @@ extern "C" int bbgr_operator_scales(int32_t kind, int32_t n_users,
 extern "C" int bbgr_pop_cdf(int32_t n_items, const int32_t *indptr_i,
                             double gamma, double *cdf, void *workspace,
                             size_t *workspace_bytes, bbgr_stream_t stream) {
-  BBGR_REQUIRE(workspace_bytes && n_items > 0, "bbgr_pop_cdf: bad args");
+  BBGR_REQUIRE(n_items > 0, "bbgr_pop_cdf: bad args");
   hipStream_t st = as_stream(stream);
-  size_t temp = 0;
-  BBGR_HIP(hipcub::DeviceScan::InclusiveSum(nullptr, temp, (double *)nullptr,
-                                            (double *)nullptr, n_items, st));
-  const size_t a = align_up(8 * (size_t)n_items);
-  const size_t need = 2 * a + align_up(temp);
-  if (!workspace) {
-    *workspace_bytes = need;
-    return BBGR_OK;
-  }
-  if (*workspace_bytes < need) {
-    set_error("bbgr_pop_cdf: workspace %zu < %zu", *workspace_bytes, need);
-    return BBGR_ERR_WORKSPACE;
-  }
+  hipError_t sizing;
+  const size_t temp = hcub::inclusive_sum_temp<double *, double *>(n_items, &sizing);
+  BBGR_HIP(sizing);
+  Carver C;
+  const size_t off_w = C.take_n<double>((size_t)n_items);
+  const size_t off_scan = C.take_n<double>((size_t)n_items);
+  const size_t off_tmp = C.take(temp);
+  bool query;
+  const int rc = take_workspace("bbgr_pop_cdf", C.used, workspace, workspace_bytes, &query);
+  if (rc || query) return rc;
   BBGR_REQUIRE(indptr_i && cdf, "bbgr_pop_cdf: null arrays");
-  char *ws = (char *)workspace;
-  double *w = (double *)ws;
-  double *scan = (double *)(ws + a);
+  double *w = ws_at<double>(workspace, off_w);
+  double *scan = ws_at<double>(workspace, off_scan);
   hipLaunchKernelGGL(pop_weight_kernel, dim3(blocks_for(n_items)), dim3(256), 0, st,
                      n_items, indptr_i, gamma, w);
   BBGR_LAUNCHED("pop_weight_kernel");
-  BBGR_HIP(hipcub::DeviceScan::InclusiveSum(ws + 2 * a, temp, w, scan, n_items, st));
+  BBGR_HIP(hcub::inclusive_sum(ws_at<char>(workspace, off_tmp), temp, w, scan, n_items, st));
   hipLaunchKernelGGL(cdf_normalise_kernel, dim3(blocks_for(n_items)), dim3(256), 0,
                      st, n_items, (const double *)scan, cdf);
   BBGR_LAUNCHED("cdf_normalise_kernel");
@@ -664,34 +648,27 @@ extern "C" int bbgr_sample_dev(int64_t batch, const int64_t *users,
 extern "C" int bbgr_shuffle(int64_t n, const int64_t *in, int64_t *out,
                             uint64_t seed, uint64_t counter, void *workspace,
                             size_t *workspace_bytes, bbgr_stream_t stream) {
-  BBGR_REQUIRE(workspace_bytes && n >= 0 && n < 2147483647LL, "bbgr_shuffle: bad args");
+  BBGR_REQUIRE(n >= 0 && n < 2147483647LL, "bbgr_shuffle: bad args");
   hipStream_t st = as_stream(stream);
-  size_t temp = 0;
-  BBGR_HIP(hipcub::DeviceRadixSort::SortPairs(
-      nullptr, temp, (unsigned long long *)nullptr, (unsigned long long *)nullptr,
-      (long *)nullptr, (long *)nullptr, (int)(n > 0 ? n : 1), 0, 64, st));
-  const size_t a = align_up(8 * (size_t)(n > 0 ? n : 1));
-  const size_t need = 2 * a + align_up(temp);
-  if (!workspace) {
-    *workspace_bytes = need;
-    return BBGR_OK;
-  }
-  if (*workspace_bytes < need) {
-    set_error("bbgr_shuffle: workspace %zu < %zu", *workspace_bytes, need);
-    return BBGR_ERR_WORKSPACE;
-  }
-  if (n == 0) return BBGR_OK;
+  const size_t m = (size_t)(n > 0 ? n : 1);
+  hipError_t sizing;
+  const size_t temp = hcub::sort_pairs_temp<unsigned long long, long>((int)m, 0, 64, &sizing);
+  BBGR_HIP(sizing);
+  Carver C;
+  const size_t off_k1 = C.take_n<unsigned long long>(m), off_k2 = C.take_n<unsigned long long>(m);
+  const size_t off_tmp = C.take(temp);
+  bool query;
+  const int rc = take_workspace("bbgr_shuffle", C.used, workspace, workspace_bytes, &query);
+  if (rc || query || n == 0) return rc;
   BBGR_REQUIRE(in && out, "bbgr_shuffle: null arrays");
-  char *ws = (char *)workspace;
-  auto *k1 = (unsigned long long *)ws;
-  auto *k2 = (unsigned long long *)(ws + a);
+  auto *k1 = ws_at<unsigned long long>(workspace, off_k1);
+  auto *k2 = ws_at<unsigned long long>(workspace, off_k2);
   hipLaunchKernelGGL(shuffle_keys_kernel, dim3(blocks_for(n)), dim3(256), 0, st,
                      (long)n, (unsigned long long)seed, (unsigned long long)counter,
                      k1);
   BBGR_LAUNCHED("shuffle_keys_kernel");
-  BBGR_HIP(hipcub::DeviceRadixSort::SortPairs(ws + 2 * a, temp, k1, k2,
-                                              (const long *)in, (long *)out, (int)n,
-                                              0, 64, st));
+  BBGR_HIP(hcub::sort_pairs(ws_at<char>(workspace, off_tmp), temp, k1, k2, (const long *)in,
+                            (long *)out, (int)n, 0, 64, st));
   return BBGR_OK;
 }
 
@@ -749,59 +726,47 @@ extern "C" int bbgr_slots_from_perms(int64_t nnz, const int32_t *perm_a, const i
 extern "C" int bbgr_nonempty_rows(int32_t n_rows, const int32_t *indptr,
                                   int64_t *out, int64_t *count, void *workspace,
                                   size_t *workspace_bytes, bbgr_stream_t stream) {
-  BBGR_REQUIRE(workspace_bytes && n_rows >= 0, "bbgr_nonempty_rows: bad args");
+  BBGR_REQUIRE(n_rows >= 0, "bbgr_nonempty_rows: bad args");
   hipStream_t st = as_stream(stream);
   hipcub::CountingInputIterator<long> it(0);
   NonEmpty sel{indptr};
-  size_t temp = 0;
-  BBGR_HIP(hipcub::DeviceSelect::If(nullptr, temp, it, (long *)nullptr,
-                                    (long *)nullptr, n_rows > 0 ? n_rows : 1, sel, st));
-  const size_t need = align_up(temp);
-  if (!workspace) {
-    *workspace_bytes = need;
-    return BBGR_OK;
-  }
-  if (*workspace_bytes < need) {
-    set_error("bbgr_nonempty_rows: workspace %zu < %zu", *workspace_bytes, need);
-    return BBGR_ERR_WORKSPACE;
-  }
+  hipError_t sizing;
+  const size_t temp =
+      hcub::select_if_temp<long *, long *>(it, n_rows > 0 ? n_rows : 1, sel, &sizing);
+  BBGR_HIP(sizing);
+  bool query;
+  const int rc =
+      take_workspace("bbgr_nonempty_rows", align_up(temp), workspace, workspace_bytes, &query);
+  if (rc || query) return rc;
   BBGR_REQUIRE(indptr && out && count, "bbgr_nonempty_rows: null arrays");
   if (n_rows == 0) {
     BBGR_HIP(hipMemsetAsync(count, 0, 8, st));
     return BBGR_OK;
   }
-  BBGR_HIP(hipcub::DeviceSelect::If(workspace, temp, it, (long *)out, (long *)count,
-                                    n_rows, sel, st));
+  BBGR_HIP(hcub::select_if(workspace, temp, it, (long *)out, (long *)count, n_rows, sel, st));
   return BBGR_OK;
 }
 
 extern "C" int bbgr_mask_to_list(int64_t n, const uint8_t *mask, int64_t *out,
                                  int64_t *count, void *workspace, size_t *workspace_bytes,
                                  bbgr_stream_t stream) {
-  BBGR_REQUIRE(workspace_bytes && n >= 0 && n < (int64_t)1 << 31,
-               "bbgr_mask_to_list: bad args");
+  BBGR_REQUIRE(n >= 0 && n < (int64_t)1 << 31, "bbgr_mask_to_list: bad args");
   hipStream_t st = as_stream(stream);
   hipcub::CountingInputIterator<long> it(0);
   Flagged sel{mask};
-  size_t temp = 0;
-  BBGR_HIP(hipcub::DeviceSelect::If(nullptr, temp, it, (long *)nullptr, (long *)nullptr,
-                                    n > 0 ? (int)n : 1, sel, st));
-  const size_t need = align_up(temp);
-  if (!workspace) {
-    *workspace_bytes = need;
-    return BBGR_OK;
-  }
-  if (*workspace_bytes < need) {
-    set_error("bbgr_mask_to_list: workspace %zu < %zu", *workspace_bytes, need);
-    return BBGR_ERR_WORKSPACE;
-  }
+  hipError_t sizing;
+  const size_t temp = hcub::select_if_temp<long *, long *>(it, n > 0 ? (int)n : 1, sel, &sizing);
+  BBGR_HIP(sizing);
+  bool query;
+  const int rc =
+      take_workspace("bbgr_mask_to_list", align_up(temp), workspace, workspace_bytes, &query);
+  if (rc || query) return rc;
   BBGR_REQUIRE(mask && out && count, "bbgr_mask_to_list: null arrays");
   if (n == 0) {
     BBGR_HIP(hipMemsetAsync(count, 0, 8, st));
     return BBGR_OK;
   }
-  BBGR_HIP(hipcub::DeviceSelect::If(workspace, temp, it, (long *)out, (long *)count, (int)n,
-                                    sel, st));
+  BBGR_HIP(hcub::select_if(workspace, temp, it, (long *)out, (long *)count, (int)n, sel, st));
   return BBGR_OK;
 }
 
@@ -846,62 +811,42 @@ __global__ void degree_runs_kernel(int n_max, const unsigned *key, const int *co
 // HBM-streaming passes instead. Counts are exact either way.
 constexpr long DEG_SORT_MIN = 1L << 22;
 
-struct DegreeSortWs {
-  size_t keys, uniq, cnt, runs, temp, total;
-};
-
-static DegreeSortWs degree_sort_ws(long n_ids, int n, int end_bit) {
-  DegreeSortWs w = {};
-  size_t t_sort = 0, t_rle = 0;
-  // size queries (no launch; the sizes are what they return)
-  (void)hipcub::DeviceRadixSort::SortKeys(nullptr, t_sort, (const unsigned *)nullptr,
-                                          (unsigned *)nullptr, (int)n_ids, 0, end_bit);
-  (void)hipcub::DeviceRunLengthEncode::Encode(nullptr, t_rle, (const unsigned *)nullptr,
-                                              (unsigned *)nullptr, (int *)nullptr, (int *)nullptr,
-                                              (int)n_ids);
-  w.keys = align_up(4 * (size_t)n_ids);
-  w.uniq = align_up(4 * (size_t)n);
-  w.cnt = align_up(4 * (size_t)n);
-  w.runs = align_up(8);
-  w.temp = align_up(t_sort > t_rle ? t_sort : t_rle);
-  w.total = w.keys + w.uniq + w.cnt + w.runs + w.temp;
-  return w;
-}
-
 extern "C" int bbgr_degree_count_ws(int64_t n_ids, const int32_t *ids, int32_t n,
                                     int32_t *degree, void *workspace, size_t *workspace_bytes,
                                     bbgr_stream_t stream) {
-  BBGR_REQUIRE(workspace_bytes && n_ids >= 0 && n >= 0 && n_ids < (1LL << 31),
-               "bbgr_degree_count_ws: bad args");
+  BBGR_REQUIRE(n_ids >= 0 && n >= 0 && n_ids < (1LL << 31), "bbgr_degree_count_ws: bad args");
   const bool by_sort = n_ids >= DEG_SORT_MIN && n > 0;
   int end_bit = 1;
   while (end_bit < 32 && (1ull << end_bit) < (unsigned long long)n) ++end_bit;
-  const DegreeSortWs sw = by_sort ? degree_sort_ws(n_ids, n, end_bit) : DegreeSortWs{};
-  const size_t need = by_sort ? sw.total : (size_t)DEG_COPIES * 4 * (size_t)(n > 0 ? n : 1);
-  if (!workspace) {
-    *workspace_bytes = need;
-    return BBGR_OK;
+  // by sort: the sorted ids, the runs' ids and lengths, their count, the larger
+  // temp of the two primitives; else the DEG_COPIES counter copies (not rounded)
+  Carver C;
+  size_t off_keys = 0, off_uniq = 0, off_cnt = 0, off_runs = 0, off_tmp = 0, t_max = 0;
+  if (by_sort) {
+    const size_t t_sort = hcub::sort_keys_temp<unsigned>((int)n_ids, 0, end_bit);
+    const size_t t_rle =
+        hcub::run_length_encode_temp<const unsigned *, unsigned *, int *, int *>((int)n_ids);
+    t_max = align_up(t_sort > t_rle ? t_sort : t_rle);
+    off_keys = C.take_n<unsigned>((size_t)n_ids);
+    off_uniq = C.take_n<unsigned>((size_t)n);
+    off_cnt = C.take_n<int>((size_t)n);
+    off_runs = C.take(8);
+    off_tmp = C.take(t_max);
   }
-  if (*workspace_bytes < need) {
-    set_error("bbgr_degree_count_ws: workspace %zu < %zu", *workspace_bytes, need);
-    return BBGR_ERR_WORKSPACE;
-  }
-  if (n == 0) return BBGR_OK;
+  const size_t need = by_sort ? C.used : (size_t)DEG_COPIES * 4 * (size_t)(n > 0 ? n : 1);
+  bool query;
+  const int rc = take_workspace("bbgr_degree_count_ws", need, workspace, workspace_bytes, &query);
+  if (rc || query || n == 0) return rc;
   BBGR_REQUIRE(degree && (n_ids == 0 || ids), "bbgr_degree_count_ws: null arrays");
   hipStream_t st = as_stream(stream);
   if (by_sort) {   // (ids are in [0, n): the caller's contract, as for the atomics)
-    char *ws = static_cast<char *>(workspace);
-    unsigned *keys = reinterpret_cast<unsigned *>(ws);
-    unsigned *uniq = reinterpret_cast<unsigned *>(ws + sw.keys);
-    int *cnt = reinterpret_cast<int *>(ws + sw.keys + sw.uniq);
-    int *runs = reinterpret_cast<int *>(ws + sw.keys + sw.uniq + sw.cnt);
-    void *temp = ws + sw.keys + sw.uniq + sw.cnt + sw.runs;
-    size_t t = sw.temp;
-    BBGR_HIP(hipcub::DeviceRadixSort::SortKeys(temp, t, reinterpret_cast<const unsigned *>(ids),
-                                               keys, (int)n_ids, 0, end_bit, st));
-    t = sw.temp;
-    BBGR_HIP(hipcub::DeviceRunLengthEncode::Encode(temp, t, keys, uniq, cnt, runs, (int)n_ids,
-                                                   st));
+    unsigned *keys = ws_at<unsigned>(workspace, off_keys);
+    unsigned *uniq = ws_at<unsigned>(workspace, off_uniq);
+    int *cnt = ws_at<int>(workspace, off_cnt), *runs = ws_at<int>(workspace, off_runs);
+    void *temp = ws_at<char>(workspace, off_tmp);
+    BBGR_HIP(hcub::sort_keys(temp, t_max, reinterpret_cast<const unsigned *>(ids), keys,
+                             (int)n_ids, 0, end_bit, st));
+    BBGR_HIP(hcub::run_length_encode(temp, t_max, keys, uniq, cnt, runs, (int)n_ids, st));
     BBGR_HIP(hipMemsetAsync(degree, 0, 4 * (size_t)n, st));
     hipLaunchKernelGGL(degree_runs_kernel, dim3(blocks_for(n)), dim3(256), 0, st, (int)n,
                        (const unsigned *)uniq, (const int *)cnt, (const int *)runs, (int)n,
@@ -939,36 +884,27 @@ extern "C" int bbgr_degree_count(int64_t n_ids, const int32_t *ids, int32_t n,
 extern "C" int bbgr_degree_order(int32_t n, const int32_t *degree, int32_t *perm,
                                  int32_t *rank, void *workspace, size_t *workspace_bytes,
                                  bbgr_stream_t stream) {
-  BBGR_REQUIRE(workspace_bytes && n >= 0, "bbgr_degree_order: bad args");
+  BBGR_REQUIRE(n >= 0, "bbgr_degree_order: bad args");
   hipStream_t st = as_stream(stream);
   const int m = n > 0 ? n : 1;
-  size_t temp = 0;
-  BBGR_HIP(hipcub::DeviceRadixSort::SortPairsDescending(
-      nullptr, temp, (const unsigned *)nullptr, (unsigned *)nullptr, (const int *)nullptr,
-      (int *)nullptr, m, 0, 32, st));
-  const size_t off_k = 0;
-  const size_t off_v = align_up(off_k + 4 * (size_t)m);
-  const size_t off_t = align_up(off_v + 4 * (size_t)m);
-  const size_t need = align_up(off_t + temp);
-  if (!workspace) {
-    *workspace_bytes = need;
-    return BBGR_OK;
-  }
-  if (*workspace_bytes < need) {
-    set_error("bbgr_degree_order: workspace %zu < %zu", *workspace_bytes, need);
-    return BBGR_ERR_WORKSPACE;
-  }
-  if (n == 0) return BBGR_OK;
+  hipError_t sizing;
+  const size_t temp = hcub::sort_pairs_descending_temp<unsigned, int>(m, 0, 32, &sizing);
+  BBGR_HIP(sizing);
+  Carver C;
+  const size_t off_k = C.take_n<unsigned>((size_t)m), off_v = C.take_n<int>((size_t)m);
+  const size_t off_t = C.take(temp);
+  bool query;
+  const int rc = take_workspace("bbgr_degree_order", C.used, workspace, workspace_bytes, &query);
+  if (rc || query || n == 0) return rc;
   BBGR_REQUIRE(degree && perm && rank, "bbgr_degree_order: null arrays");
-  char *ws = (char *)workspace;
-  unsigned *k_out = (unsigned *)(ws + off_k);
-  int *iota = (int *)(ws + off_v);
+  unsigned *k_out = ws_at<unsigned>(workspace, off_k);
+  int *iota = ws_at<int>(workspace, off_v);
   hipLaunchKernelGGL(iota_kernel, dim3(blocks_for(n)), dim3(256), 0, st, n, iota);
   BBGR_LAUNCHED("iota_kernel");
   // radix sort is stable: equal degrees keep ascending input id
-  BBGR_HIP(hipcub::DeviceRadixSort::SortPairsDescending(
-      ws + off_t, temp, (const unsigned *)degree, k_out, (const int *)iota, (int *)perm, n, 0,
-      32, st));
+  BBGR_HIP(hcub::sort_pairs_descending(ws_at<char>(workspace, off_t), temp,
+                                       (const unsigned *)degree, k_out, (const int *)iota,
+                                       (int *)perm, n, 0, 32, st));
   hipLaunchKernelGGL(invert_perm_kernel, dim3(blocks_for(n)), dim3(256), 0, st, n,
                      (const int *)perm, (int *)rank);
   BBGR_LAUNCHED("invert_perm_kernel");

@@ -43,9 +43,8 @@
 // order-free counts: two calls give the same bits. Every offset, position and
 // index read from a workspace or a caller's buffer is clamped or checked
 // before it addresses anything.
-#include "common.h"
+#include "cub_temp.h"
 
-#include <hipcub/hipcub.hpp>
 
 namespace bbgr {
 
@@ -736,25 +735,22 @@ extern "C" int bbgr_jsonl_lines(const bbgr_jsonl_args *a, void *workspace, size_
   static const char *fn = "bbgr_jsonl_lines";
   if (int rc = jl_check(fn, a, true)) return rc;
   const long n_tiles = ((long)a->n_bytes + JL_TILE - 1) / JL_TILE;
-  size_t t_scan = 0;
-  (void)hipcub::DeviceScan::ExclusiveSum(nullptr, t_scan, (const int *)nullptr, (int *)nullptr,
-                                         (int)n_tiles, (hipStream_t) nullptr);
-  const size_t off_off = align_up(sizeof(int) * (size_t)n_tiles);
-  const size_t off_tmp = off_off + align_up(sizeof(int) * (size_t)n_tiles);
+  const size_t t_scan = hcub::exclusive_sum_temp<const int *, int *>((int)n_tiles);
+  Carver C;
+  const size_t off_count = C.take_n<int>((size_t)n_tiles), off_off = C.take_n<int>((size_t)n_tiles);
+  const size_t off_tmp = C.take(t_scan);
   bool query;
-  int rc = feat_workspace(fn, off_tmp + align_up(t_scan), workspace, workspace_bytes, &query);
+  int rc = take_workspace(fn, C.used, workspace, workspace_bytes, &query);
   if (rc || query || a->n_lines == 0) return rc;
   hipStream_t st = as_stream(stream);
-  char *ws = static_cast<char *>(workspace);
-  int *tile_count = reinterpret_cast<int *>(ws);
-  int *tile_off = reinterpret_cast<int *>(ws + off_off);
+  int *tile_count = ws_at<int>(workspace, off_count);
+  int *tile_off = ws_at<int>(workspace, off_off);
   const dim3 grid(jl_wave_blocks(n_tiles)), block(64 * JL_WAVES);
   hipLaunchKernelGGL(jsonl_tile_kernel<false>, grid, block, 0, st, (long)a->n_bytes, a->data, n_tiles,
                      tile_count, (const int *)nullptr, 0L, (int *)nullptr, (long long *)nullptr);
   BBGR_LAUNCHED("jsonl_tile_kernel<count>");
-  size_t tb = t_scan;
-  BBGR_HIP(hipcub::DeviceScan::ExclusiveSum(ws + off_tmp, tb, (const int *)tile_count, tile_off,
-                                            (int)n_tiles, st));
+  BBGR_HIP(hcub::exclusive_sum(ws_at<char>(workspace, off_tmp), t_scan, (const int *)tile_count,
+                               tile_off, (int)n_tiles, st));
   hipLaunchKernelGGL(jsonl_tile_kernel<true>, grid, block, 0, st, (long)a->n_bytes, a->data, n_tiles,
                      (int *)nullptr, (const int *)tile_off, (long)a->n_lines, a->line_end,
                      (long long *)nullptr);
@@ -783,23 +779,19 @@ extern "C" int bbgr_jsonl_offsets(const bbgr_jsonl_args *a, void *workspace,
   if (int rc = jl_check_scan(fn, a)) return rc;
   BBGR_REQUIRE_IN(fn, a->offs, "null offs");
   const long n = (long)a->n_lines;
-  size_t t_scan = 0;
-  {
-    const JlSizeIter in(hipcub::CountingInputIterator<long>(0), JlSize{nullptr, nullptr, n, 0});
-    (void)hipcub::DeviceScan::ExclusiveSum(nullptr, t_scan, in, (long long *)nullptr, (int)(n + 1),
-                                           (hipStream_t) nullptr);
-  }
+  const size_t t_scan = hcub::exclusive_sum_temp<JlSizeIter, long long *>(
+      (int)(n + 1), nullptr,
+      JlSizeIter(hipcub::CountingInputIterator<long>(0), JlSize{nullptr, nullptr, n, 0}));
   bool query;
-  int rc = feat_workspace(fn, align_up(t_scan), workspace, workspace_bytes, &query);
+  int rc = take_workspace(fn, align_up(t_scan), workspace, workspace_bytes, &query);
   if (rc || query) return rc;
   hipStream_t st = as_stream(stream);
   for (int which = 0; which < 4; ++which) {
     const JlSizeIter in(hipcub::CountingInputIterator<long>(0),
                         JlSize{a->status, a->sizes, n, which});
-    size_t tb = t_scan;
-    BBGR_HIP(hipcub::DeviceScan::ExclusiveSum(
-        workspace, tb, in, reinterpret_cast<long long *>(a->offs) + (size_t)which * (size_t)(n + 1),
-        (int)(n + 1), st));
+    BBGR_HIP(hcub::exclusive_sum(
+        workspace, t_scan, in,
+        reinterpret_cast<long long *>(a->offs) + (size_t)which * (size_t)(n + 1), (int)(n + 1), st));
   }
   return BBGR_OK;
 }
@@ -827,28 +819,6 @@ extern "C" int bbgr_jsonl_write(const bbgr_jsonl_args *a, bbgr_stream_t stream) 
   return BBGR_OK;
 }
 
-namespace {
-struct IdsWorkspace {
-  size_t k1, k2, v1, v2, head, run, run_rec, first, rank, tmp, total;
-};
-IdsWorkspace ids_workspace(long n, size_t temp) {
-  const size_t u = (size_t)n;
-  IdsWorkspace w;
-  w.k1 = 0;
-  w.k2 = w.k1 + align_up(8 * u);
-  w.v1 = w.k2 + align_up(8 * u);
-  w.v2 = w.v1 + align_up(4 * u);
-  w.head = w.v2 + align_up(4 * u);
-  w.run = w.head + align_up(4 * u);
-  w.run_rec = w.run + align_up(4 * u);
-  w.first = w.run_rec + align_up(4 * u);
-  w.rank = w.first + align_up(4 * u);
-  w.tmp = w.rank + align_up(4 * u);
-  w.total = w.tmp + align_up(temp);
-  return w;
-}
-}  // namespace
-
 extern "C" int bbgr_ids_number(int64_t n, const uint8_t *data, const int64_t *offsets,
                                int64_t data_bytes, uint64_t hash_mask, int32_t *ids,
                                int32_t *first_rec, int64_t *totals, void *workspace,
@@ -865,27 +835,28 @@ extern "C" int bbgr_ids_number(int64_t n, const uint8_t *data, const int64_t *of
   }
   size_t t_sort = 0, t_scan = 0;
   if (n > 0) {
-    (void)hipcub::DeviceRadixSort::SortPairs(
-        nullptr, t_sort, (const unsigned long long *)nullptr, (unsigned long long *)nullptr,
-        (const uint32_t *)nullptr, (uint32_t *)nullptr, (int)n, 0, 64, (hipStream_t) nullptr);
-    (void)hipcub::DeviceScan::InclusiveSum(nullptr, t_scan, (const int *)nullptr, (int *)nullptr,
-                                           (int)n, (hipStream_t) nullptr);
+    t_sort = hcub::sort_pairs_temp<unsigned long long, uint32_t>((int)n, 0, 64);
+    t_scan = hcub::inclusive_sum_temp<const int *, int *>((int)n);
   }
   const size_t temp = t_sort > t_scan ? t_sort : t_scan;
-  const IdsWorkspace W = ids_workspace((long)n, temp);
+  const size_t u = (size_t)n;
+  Carver C;
+  const size_t off_k1 = C.take_n<unsigned long long>(u), off_k2 = C.take_n<unsigned long long>(u);
+  const size_t off_v1 = C.take_n<uint32_t>(u), off_v2 = C.take_n<uint32_t>(u);
+  const size_t off_head = C.take_n<int>(u), off_run = C.take_n<int>(u);
+  const size_t off_run_rec = C.take_n<int>(u), off_first = C.take_n<int>(u);
+  const size_t off_rank = C.take_n<int>(u), off_tmp = C.take(temp);
   bool query;
-  int rc = feat_workspace(fn, W.total, workspace, workspace_bytes, &query);
+  int rc = take_workspace(fn, C.used, workspace, workspace_bytes, &query);
   if (rc || query || n == 0) return rc;
   hipStream_t st = as_stream(stream);
-  char *ws = static_cast<char *>(workspace);
-  unsigned long long *k1 = reinterpret_cast<unsigned long long *>(ws + W.k1);
-  unsigned long long *k2 = reinterpret_cast<unsigned long long *>(ws + W.k2);
-  uint32_t *v1 = reinterpret_cast<uint32_t *>(ws + W.v1);
-  uint32_t *v2 = reinterpret_cast<uint32_t *>(ws + W.v2);
-  int *head = reinterpret_cast<int *>(ws + W.head), *run = reinterpret_cast<int *>(ws + W.run);
-  int *run_rec = reinterpret_cast<int *>(ws + W.run_rec);
-  int *first = reinterpret_cast<int *>(ws + W.first), *rank = reinterpret_cast<int *>(ws + W.rank);
-  void *tmp = ws + W.tmp;
+  unsigned long long *k1 = ws_at<unsigned long long>(workspace, off_k1);
+  unsigned long long *k2 = ws_at<unsigned long long>(workspace, off_k2);
+  uint32_t *v1 = ws_at<uint32_t>(workspace, off_v1), *v2 = ws_at<uint32_t>(workspace, off_v2);
+  int *head = ws_at<int>(workspace, off_head), *run = ws_at<int>(workspace, off_run);
+  int *run_rec = ws_at<int>(workspace, off_run_rec);
+  int *first = ws_at<int>(workspace, off_first), *rank = ws_at<int>(workspace, off_rank);
+  void *tmp = ws_at<char>(workspace, off_tmp);
   const IdsParams P{(long)n, data, reinterpret_cast<const long long *>(offsets), (long)data_bytes,
                     hash_mask ? hash_mask : ~0ull};
   const dim3 grid((unsigned)((n + 255) / 256)), block(256);
@@ -894,16 +865,13 @@ extern "C" int bbgr_ids_number(int64_t n, const uint8_t *data, const int64_t *of
   BBGR_HIP(hipMemsetAsync(run_rec, 0, sizeof(int) * (size_t)n, st));
   hipLaunchKernelGGL(ids_hash_kernel, grid, block, 0, st, P, k1, v1);
   BBGR_LAUNCHED("ids_hash_kernel");
-  size_t tb = temp;
-  BBGR_HIP(hipcub::DeviceRadixSort::SortPairs(tmp, tb, (const unsigned long long *)k1, k2,
-                                              (const uint32_t *)v1, v2, (int)n, 0, 64, st));
+  BBGR_HIP(hcub::sort_pairs(tmp, temp, (const unsigned long long *)k1, k2, (const uint32_t *)v1,
+                            v2, (int)n, 0, 64, st));
   hipLaunchKernelGGL(ids_verify_kernel, grid, block, 0, st, P, (const unsigned long long *)k2,
                      (const uint32_t *)v2, head, first, reinterpret_cast<long long *>(totals));
   BBGR_LAUNCHED("ids_verify_kernel");
-  tb = temp;
-  BBGR_HIP(hipcub::DeviceScan::InclusiveSum(tmp, tb, (const int *)head, run, (int)n, st));
-  tb = temp;
-  BBGR_HIP(hipcub::DeviceScan::ExclusiveSum(tmp, tb, (const int *)first, rank, (int)n, st));
+  BBGR_HIP(hcub::inclusive_sum(tmp, temp, (const int *)head, run, (int)n, st));
+  BBGR_HIP(hcub::exclusive_sum(tmp, temp, (const int *)first, rank, (int)n, st));
   hipLaunchKernelGGL(ids_heads_kernel, grid, block, 0, st, (long)n, (const uint32_t *)v2,
                      (const int *)head, (const int *)run, run_rec);
   BBGR_LAUNCHED("ids_heads_kernel");
@@ -933,18 +901,15 @@ extern "C" int bbgr_ids_table(int64_t n_ids, const int32_t *first_rec, int64_t n
   const IdLenIter in(hipcub::CountingInputIterator<long>(0),
                      IdLen{first_rec, reinterpret_cast<const long long *>(offsets), (long)n_ids,
                            (long)n});
-  size_t t_scan = 0;
-  (void)hipcub::DeviceScan::ExclusiveSum(nullptr, t_scan, in, (long long *)nullptr,
-                                         (int)(n_ids + 1), (hipStream_t) nullptr);
+  const size_t t_scan =
+      hcub::exclusive_sum_temp<IdLenIter, long long *>((int)(n_ids + 1), nullptr, in);
   bool query;
-  int rc = feat_workspace(fn, align_up(t_scan), workspace, workspace_bytes, &query);
+  int rc = take_workspace(fn, align_up(t_scan), workspace, workspace_bytes, &query);
   if (rc || query) return rc;
   hipStream_t st = as_stream(stream);
   if (!tab_data) {   // the offsets alone: tab_offsets[n_ids] sizes the table
-    size_t tb = t_scan;
-    BBGR_HIP(hipcub::DeviceScan::ExclusiveSum(workspace, tb, in,
-                                              reinterpret_cast<long long *>(tab_offsets),
-                                              (int)(n_ids + 1), st));
+    BBGR_HIP(hcub::exclusive_sum(workspace, t_scan, in, reinterpret_cast<long long *>(tab_offsets),
+                                 (int)(n_ids + 1), st));
     return BBGR_OK;
   }
   if (n_ids == 0 || tab_bytes == 0) return BBGR_OK;

@@ -96,16 +96,12 @@ static RecLayout rec_layout(long n_users, int n_items, int k, int cus, int block
   L.splits = full_splits((long)nb, n_items, cus, block_users);
   L.km = rec_km(k);
   const size_t n = nb * L.splits * 2 * L.km;
-  size_t off = 0;
-  L.lscore = off;
-  off = align_up(off + sizeof(float) * n);
-  L.litem = off;
-  off = align_up(off + sizeof(int) * n);
-  L.bscore = off;
-  off = align_up(off + sizeof(float) * nb);
-  L.bitem = off;
-  off = align_up(off + sizeof(int) * nb);
-  L.total = off;
+  Carver C;
+  L.lscore = C.take_n<float>(n);
+  L.litem = C.take_n<int>(n);
+  L.bscore = C.take_n<float>(nb);
+  L.bitem = C.take_n<int>(nb);
+  L.total = C.used;
   return L;
 }
 
@@ -159,16 +155,10 @@ template <typename Args, typename Launch>
 static int rec_run(const char *who, const Args *a, void *workspace, size_t *workspace_bytes,
                    int block_users, bbgr_stream_t stream, Launch &&launch) {
   const RecLayout L = rec_layout(a->n_users, a->n_items, a->k, device_cus(), block_users);
-  if (!workspace) {
-    *workspace_bytes = L.total;
-    return BBGR_OK;
-  }
-  if (*workspace_bytes < L.total) {
-    set_error("%s: workspace %zu < %zu bytes", who, *workspace_bytes, L.total);
-    return BBGR_ERR_WORKSPACE;
-  }
+  bool query;
+  if (int rc = take_workspace(who, L.total, workspace, workspace_bytes, &query)) return rc;
+  if (query) return BBGR_OK;
   hipStream_t st = as_stream(stream);
-  char *ws = static_cast<char *>(workspace);
   for (long b0 = 0; b0 < a->n_users; b0 += L.batch) {
     RecParams P;
     P.n_users = a->n_users - b0 < L.batch ? a->n_users - b0 : L.batch;
@@ -184,10 +174,10 @@ static int rec_run(const char *who, const Args *a, void *workspace, size_t *work
     P.n_splits = (int)L.splits;
     const long per = (a->n_items + L.splits - 1) / L.splits;
     P.split_items = (int)((per + FULL_TILE - 1) / FULL_TILE * FULL_TILE);
-    P.list_score = reinterpret_cast<float *>(ws + L.lscore);
-    P.list_item = reinterpret_cast<int *>(ws + L.litem);
-    P.bound_score = reinterpret_cast<float *>(ws + L.bscore);
-    P.bound_item = reinterpret_cast<int *>(ws + L.bitem);
+    P.list_score = ws_at<float>(workspace, L.lscore);
+    P.list_item = ws_at<int>(workspace, L.litem);
+    P.bound_score = ws_at<float>(workspace, L.bscore);
+    P.bound_item = ws_at<int>(workspace, L.bitem);
     for (int pos0 = 0; pos0 < a->k; pos0 += L.km) {
       P.cont = pos0 > 0;
       int rc = launch(P, L.km, st);

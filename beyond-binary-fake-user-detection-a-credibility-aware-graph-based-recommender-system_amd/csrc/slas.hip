@@ -413,19 +413,6 @@ __global__ __launch_bounds__(256) void slas_induce_fill_kernel(bbgr_slas_induce_
   }
 }
 
-struct InduceLayout {
-  size_t counts, offs, total;
-};
-
-static InduceLayout induce_layout(long n) {
-  InduceLayout L{};
-  const size_t m = (size_t)(n > 0 ? n : 0) + 1;
-  L.counts = 0;
-  L.offs = align_up(sizeof(long long) * m);
-  L.total = align_up(L.offs + sizeof(long long) * m);
-  return L;
-}
-
 static bool view_ok(int view) {
   return view == BBGR_SLAS_VIEW_NONE || view == BBGR_SLAS_VIEW_EARLY ||
          view == BBGR_SLAS_VIEW_LATE;
@@ -533,25 +520,21 @@ extern "C" int bbgr_slas_induce(const bbgr_slas_induce_args *a, void *workspace,
   BBGR_REQUIRE(a->capacity >= 0, "bbgr_slas_induce: capacity < 0");
   BBGR_REQUIRE((a->out_edges == nullptr) == (a->out_eid == nullptr),
                "bbgr_slas_induce: out_edges and out_eid must be given together");
-  const InduceLayout L = induce_layout(a->n_users_listed);
-  if (!workspace) {
-    *workspace_bytes = L.total;
-    return BBGR_OK;
-  }
-  if (*workspace_bytes < L.total) {
-    set_error("bbgr_slas_induce: workspace %zu < %zu bytes", *workspace_bytes, L.total);
-    return BBGR_ERR_WORKSPACE;
-  }
-  if (a->n_users_listed == 0) return BBGR_OK;
+  // per listed user (and one more) the count of its induced edges, then their scan
+  Carver C;
+  const size_t off_counts = C.take_n<long long>((size_t)a->n_users_listed + 1);
+  const size_t off_offs = C.take_n<long long>((size_t)a->n_users_listed + 1);
+  bool query;
+  const int rc = take_workspace("bbgr_slas_induce", C.used, workspace, workspace_bytes, &query);
+  if (rc || query || a->n_users_listed == 0) return rc;
   BBGR_REQUIRE(a->users, "bbgr_slas_induce: null users");
   BBGR_REQUIRE(a->item_local, "bbgr_slas_induce: null item_local");
   BBGR_REQUIRE(a->indptr, "bbgr_slas_induce: null indptr");
   BBGR_REQUIRE(a->nbr, "bbgr_slas_induce: null nbr");
   BBGR_REQUIRE(a->eid, "bbgr_slas_induce: null eid");
   hipStream_t st = as_stream(stream);
-  char *ws = static_cast<char *>(workspace);
-  long long *counts = reinterpret_cast<long long *>(ws + L.counts);
-  long long *offs = reinterpret_cast<long long *>(ws + L.offs);
+  long long *counts = ws_at<long long>(workspace, off_counts);
+  long long *offs = ws_at<long long>(workspace, off_offs);
   const dim3 grid((unsigned)((a->n_users_listed + 3) / 4));
   if (!a->out_edges) {   // count + scan: the caller sizes the outputs from *count
     BBGR_REQUIRE(a->count, "bbgr_slas_induce: null count");

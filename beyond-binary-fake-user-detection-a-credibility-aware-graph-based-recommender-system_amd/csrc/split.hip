@@ -396,7 +396,6 @@ __global__ __launch_bounds__(256) void split_scatter_kernel(bbgr_split_args A, c
   }
 }
 
-static size_t split_code_bytes(long n) { return align_up((size_t)n); }
 static long split_tiles(long n) { return (n + SPLIT_TILE - 1) / SPLIT_TILE; }
 
 }  // namespace bbgr
@@ -463,14 +462,16 @@ extern "C" int bbgr_split_edges(const bbgr_split_args *a, void *workspace,
     BBGR_REQUIRE_IN(fn, a->counts, "null counts");
   }
   const long n = (long)a->n, n_tiles = split_tiles(n);
-  const size_t off_tiles = split_code_bytes(n);
+  // one code byte per record, then SPLIT_NC counts per tile (and one tile more)
+  Carver C;
+  const size_t off_code = C.take((size_t)n);
+  const size_t off_tiles = C.take_n<int>(SPLIT_NC * (size_t)(n_tiles + 1));
   bool query;
-  int rc = feat_workspace(fn, off_tiles + align_up(sizeof(int) * SPLIT_NC * (size_t)(n_tiles + 1)),
-                          workspace, workspace_bytes, &query);
+  int rc = take_workspace(fn, C.used, workspace, workspace_bytes, &query);
   if (rc || query || n == 0) return rc;
   hipStream_t st = as_stream(stream);
-  uint8_t *code = static_cast<uint8_t *>(workspace);
-  int *tiles = reinterpret_cast<int *>(static_cast<char *>(workspace) + off_tiles);
+  uint8_t *code = ws_at<uint8_t>(workspace, off_code);
+  int *tiles = ws_at<int>(workspace, off_tiles);
   long long *totals = reinterpret_cast<long long *>(a->counts);
   BBGR_HIP(hipMemsetAsync(a->user_map, 0xff, sizeof(int) * (size_t)a->n_users, st));
   BBGR_HIP(hipMemsetAsync(a->item_map, 0xff, sizeof(int) * (size_t)a->n_items, st));

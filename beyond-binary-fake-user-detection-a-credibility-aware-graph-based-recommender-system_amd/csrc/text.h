@@ -133,18 +133,20 @@ struct RowBound {
 // storage: token offsets [n + 1], then per token its record, its start, the
 // hash and the token index before (k1, v1) and after (k2, v2) the sort.
 struct TextWorkspace {
-  size_t off_rec, off_pos, off_k1, off_k2, off_v1, off_v2, off_tmp;
+  size_t off_tok, off_rec, off_pos, off_k1, off_k2, off_v1, off_v2, off_tmp;
 };
 
 inline TextWorkspace text_workspace(long n, size_t nt) {
   TextWorkspace w;
-  w.off_rec = align_up(sizeof(int) * (size_t)(n + 1));
-  w.off_pos = w.off_rec + align_up(sizeof(int) * nt);
-  w.off_k1 = w.off_pos + align_up(sizeof(uint32_t) * nt);
-  w.off_k2 = w.off_k1 + align_up(sizeof(unsigned long long) * nt);
-  w.off_v1 = w.off_k2 + align_up(sizeof(unsigned long long) * nt);
-  w.off_v2 = w.off_v1 + align_up(sizeof(uint32_t) * nt);
-  w.off_tmp = w.off_v2 + align_up(sizeof(uint32_t) * nt);
+  Carver C;
+  w.off_tok = C.take_n<int>((size_t)(n + 1));
+  w.off_rec = C.take_n<int>(nt);
+  w.off_pos = C.take_n<uint32_t>(nt);
+  w.off_k1 = C.take_n<unsigned long long>(nt);
+  w.off_k2 = C.take_n<unsigned long long>(nt);
+  w.off_v1 = C.take_n<uint32_t>(nt);
+  w.off_v2 = C.take_n<uint32_t>(nt);
+  w.off_tmp = C.used;
   return w;
 }
 
@@ -152,7 +154,6 @@ inline TextWorkspace text_workspace(long n, size_t nt) {
 // `workspace`.
 inline TextTokens text_tokens(const bbgr_text_args *a, void *workspace, const TextWorkspace &W,
                               int T) {
-  const char *ws = static_cast<const char *>(workspace);
   TextTokens K;
   K.n = (long)a->n;
   K.total = T;
@@ -160,9 +161,9 @@ inline TextTokens text_tokens(const bbgr_text_args *a, void *workspace, const Te
   K.offsets = reinterpret_cast<const long long *>(a->offsets);
   K.first = (long)a->first;
   K.last = (long)a->last;
-  K.tok_pos = reinterpret_cast<const uint32_t *>(ws + W.off_pos);
-  K.tok_rec = reinterpret_cast<const int *>(ws + W.off_rec);
-  K.tok_off = reinterpret_cast<const int *>(ws);
+  K.tok_pos = ws_at<const uint32_t>(workspace, W.off_pos);
+  K.tok_rec = ws_at<const int>(workspace, W.off_rec);
+  K.tok_off = ws_at<const int>(workspace, W.off_tok);
   K.hash_mask = a->hash_mask ? a->hash_mask : ~0ull;
   return K;
 }

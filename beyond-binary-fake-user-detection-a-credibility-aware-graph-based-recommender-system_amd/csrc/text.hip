@@ -37,10 +37,9 @@
 //
 // Integer work only; the integer atomics add order-free sums: two calls give
 // the same bits. Measured in DESIGN 4f (tools/text_bench.py).
-#include "common.h"
+#include "cub_temp.h"
 #include "text.h"
 
-#include <hipcub/hipcub.hpp>
 #include <limits.h>
 
 namespace bbgr {
@@ -257,38 +256,30 @@ static int text_unique(const char *fn, const bbgr_text_args *a, int64_t total_to
   const size_t nt = (size_t)T;
   size_t t_scan = 0, t_sort = 0;
   if (n > 0) {
-    (void)hipcub::DeviceScan::InclusiveSum(nullptr, t_scan, (const int *)nullptr, (int *)nullptr,
-                                           (int)n, (hipStream_t) nullptr);
+    t_scan = hcub::inclusive_sum_temp<const int *, int *>((int)n);
     const hipcub::CountingInputIterator<int> rec(0);
     const SegIter seg_b(rec, RowBound{nullptr, T, false}), seg_e(rec, RowBound{nullptr, T, true});
-    (void)hipcub::DeviceSegmentedRadixSort::SortPairs(
-        nullptr, t_sort, (const unsigned long long *)nullptr, (unsigned long long *)nullptr,
-        (const uint32_t *)nullptr, (uint32_t *)nullptr, T, (int)n, seg_b, seg_e, 0, 64,
-        (hipStream_t) nullptr);
+    t_sort = hcub::seg_sort_pairs_temp<unsigned long long, uint32_t>(T, (int)n, seg_b, seg_e, 0, 64);
   }
   const TextWorkspace W = text_workspace(n, nt);
   const size_t temp = t_scan > t_sort ? t_scan : t_sort;
   bool query;
-  int rc = feat_workspace(fn, W.off_tmp + align_up(temp), workspace, workspace_bytes, &query);
+  int rc = take_workspace(fn, W.off_tmp + align_up(temp), workspace, workspace_bytes, &query);
   if (rc || query || n == 0) return rc;
   hipStream_t st = as_stream(stream);
-  char *ws = static_cast<char *>(workspace);
-  int *tok_off = reinterpret_cast<int *>(ws);
-  int *tok_rec = reinterpret_cast<int *>(ws + W.off_rec);
-  uint32_t *tok_pos = reinterpret_cast<uint32_t *>(ws + W.off_pos);
-  unsigned long long *k1 = reinterpret_cast<unsigned long long *>(ws + W.off_k1);
-  unsigned long long *k2 = reinterpret_cast<unsigned long long *>(ws + W.off_k2);
-  uint32_t *v1 = reinterpret_cast<uint32_t *>(ws + W.off_v1);
-  uint32_t *v2 = reinterpret_cast<uint32_t *>(ws + W.off_v2);
-  void *tmp = ws + W.off_tmp;
+  int *tok_off = ws_at<int>(workspace, W.off_tok);
+  int *tok_rec = ws_at<int>(workspace, W.off_rec);
+  uint32_t *tok_pos = ws_at<uint32_t>(workspace, W.off_pos);
+  unsigned long long *k1 = ws_at<unsigned long long>(workspace, W.off_k1);
+  unsigned long long *k2 = ws_at<unsigned long long>(workspace, W.off_k2);
+  uint32_t *v1 = ws_at<uint32_t>(workspace, W.off_v1), *v2 = ws_at<uint32_t>(workspace, W.off_v2);
+  void *tmp = ws_at<char>(workspace, W.off_tmp);
   const TextTokens K = text_tokens(a, workspace, W, T);
   const unsigned tok_blocks = (unsigned)(((long)T + 255) / 256);
   if (T > 0 && (stages & BBGR_TEXT_STAGE_EMIT)) {
     // token offsets: tok_off[0] = 0, tok_off[r + 1] = n_tokens[0] + .. + n_tokens[r]
     BBGR_HIP(hipMemsetAsync(tok_off, 0, sizeof(int), st));
-    size_t tb = temp;
-    BBGR_HIP(hipcub::DeviceScan::InclusiveSum(tmp, tb, (const int *)a->n_tokens, tok_off + 1,
-                                              (int)n, st));
+    BBGR_HIP(hcub::inclusive_sum(tmp, temp, (const int *)a->n_tokens, tok_off + 1, (int)n, st));
     TextParams P = text_params(a);
     P.tok_off = tok_off;
     P.tok_pos = tok_pos;
@@ -303,10 +294,8 @@ static int text_unique(const char *fn, const bbgr_text_args *a, int64_t total_to
   if (T > 0 && (stages & BBGR_TEXT_STAGE_SORT)) {
     const hipcub::CountingInputIterator<int> rec(0);
     const SegIter seg_b(rec, RowBound{tok_off, T, false}), seg_e(rec, RowBound{tok_off, T, true});
-    size_t tb = temp;
-    BBGR_HIP(hipcub::DeviceSegmentedRadixSort::SortPairs(
-        tmp, tb, (const unsigned long long *)k1, k2, (const uint32_t *)v1, v2, T, (int)n, seg_b,
-        seg_e, 0, 64, st));
+    BBGR_HIP(hcub::seg_sort_pairs(tmp, temp, (const unsigned long long *)k1, k2,
+                                  (const uint32_t *)v1, v2, T, (int)n, seg_b, seg_e, 0, 64, st));
   }
   if (!(stages & BBGR_TEXT_STAGE_VERIFY)) return BBGR_OK;
   BBGR_HIP(hipMemsetAsync(a->n_unique_tokens, 0, sizeof(int) * (size_t)n, st));

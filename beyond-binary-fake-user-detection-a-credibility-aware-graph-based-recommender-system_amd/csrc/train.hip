@@ -4,9 +4,8 @@
 // Reference: LightGCN.bpr_loss  Version-2/lighgcn_cu_pop.py:495-508
 //            (lightgcn.py:333-349; lightgcn_cu.py:632-648 adds L_fair)
 //            opt.step()          Version-2/lighgcn_cu_pop.py:863 (Adam, :793)
-#include <hipcub/hipcub.hpp>
 
-#include "common.h"
+#include "cub_temp.h"
 
 namespace bbgr {
 
@@ -921,47 +920,46 @@ __global__ __launch_bounds__(256) void scatter_segments_kernel(long n, const uns
 using namespace bbgr;
 
 // the plan of a scatter over n rows: [k1 | k2 | v1 | v2 | sort scratch], the
-// sorted (key, position) pairs in k2 / v2
-static size_t scatter_plan_bytes(int64_t n, int64_t n_dst, int *end_bit_out, size_t *temp_out,
-                                 hipStream_t st) {
-  int end_bit = 1;   // keys are in [0, n_dst] (n_dst marks skipped rows)
-  while (end_bit < 32 && (1ull << end_bit) <= (unsigned long long)n_dst) ++end_bit;
-  size_t temp = 0;
-  (void)hipcub::DeviceRadixSort::SortPairs(nullptr, temp, (unsigned *)nullptr, (unsigned *)nullptr,
-                                           (int *)nullptr, (int *)nullptr,
-                                           (int)(n > 0 ? n : 1), 0, end_bit, st);
-  if (end_bit_out) *end_bit_out = end_bit;
-  if (temp_out) *temp_out = temp;
-  return 4 * align_up(4 * (size_t)(n > 0 ? n : 1)) + align_up(temp);
+// sorted (key, position) pairs in k2 / v2. `sized`: with the sort's scratch (a
+// hipcub size query); bbgr_scatter_apply reads the arrays before it only.
+struct ScatterPlan {
+  size_t k1, k2, v1, v2, tmp, total, temp;
+  int end_bit;
+};
+
+static ScatterPlan scatter_plan_layout(int64_t n, int64_t n_dst, bool sized = true) {
+  ScatterPlan L;
+  L.end_bit = 1;   // keys are in [0, n_dst] (n_dst marks skipped rows)
+  while (L.end_bit < 32 && (1ull << L.end_bit) <= (unsigned long long)n_dst) ++L.end_bit;
+  const size_t m = (size_t)(n > 0 ? n : 1);
+  L.temp = sized ? hcub::sort_pairs_temp<unsigned, int>((int)m, 0, L.end_bit) : 0;
+  Carver C;
+  L.k1 = C.take_n<unsigned>(m);
+  L.k2 = C.take_n<unsigned>(m);
+  L.v1 = C.take_n<int>(m);
+  L.v2 = C.take_n<int>(m);
+  L.tmp = C.take(L.temp);
+  L.total = C.used;
+  return L;
 }
 
 extern "C" int bbgr_scatter_plan(int64_t n, const int64_t *idx, int64_t n_dst, void *plan,
                                  size_t *plan_bytes, bbgr_stream_t stream) {
-  BBGR_REQUIRE(n >= 0 && n < (1ll << 31) && n_dst >= 0 && n_dst < 0xFFFFFFFFll && plan_bytes,
+  BBGR_REQUIRE(n >= 0 && n < (1ll << 31) && n_dst >= 0 && n_dst < 0xFFFFFFFFll,
                "bbgr_scatter_plan: bad sizes");
   hipStream_t st = as_stream(stream);
-  int end_bit = 1;
-  size_t temp = 0;
-  const size_t need = scatter_plan_bytes(n, n_dst, &end_bit, &temp, st);
-  if (!plan) {
-    *plan_bytes = need;
-    return BBGR_OK;
-  }
-  if (*plan_bytes < need) {
-    set_error("bbgr_scatter_plan: plan %zu < %zu bytes", *plan_bytes, need);
-    return BBGR_ERR_WORKSPACE;
-  }
-  if (n == 0) return BBGR_OK;
+  const ScatterPlan L = scatter_plan_layout(n, n_dst);
+  bool query;
+  const int rc = take_workspace("bbgr_scatter_plan", L.total, plan, plan_bytes, &query);
+  if (rc || query || n == 0) return rc;
   BBGR_REQUIRE(idx, "bbgr_scatter_plan: null idx");
-  const size_t a = align_up(4 * (size_t)n);
-  char *ws = static_cast<char *>(plan);
-  unsigned *k1 = reinterpret_cast<unsigned *>(ws), *k2 = reinterpret_cast<unsigned *>(ws + a);
-  int *v1 = reinterpret_cast<int *>(ws + 2 * a), *v2 = reinterpret_cast<int *>(ws + 3 * a);
+  unsigned *k1 = ws_at<unsigned>(plan, L.k1), *k2 = ws_at<unsigned>(plan, L.k2);
+  int *v1 = ws_at<int>(plan, L.v1), *v2 = ws_at<int>(plan, L.v2);
   hipLaunchKernelGGL(scatter_keys_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
                      (long)n, (const long *)idx, (long)n_dst, k1, v1);
   BBGR_LAUNCHED("scatter_keys_kernel");
-  BBGR_HIP(hipcub::DeviceRadixSort::SortPairs(ws + 4 * a, temp, k1, k2, v1, v2, (int)n, 0,
-                                              end_bit, st));
+  BBGR_HIP(hcub::sort_pairs(ws_at<char>(plan, L.tmp), L.temp, k1, k2, v1, v2, (int)n, 0,
+                            L.end_bit, st));
   return BBGR_OK;
 }
 
@@ -978,10 +976,9 @@ extern "C" int bbgr_scatter_apply(int64_t n, int64_t n_dst, const void *plan, co
   BBGR_REQUIRE(plan && src && dst, "bbgr_scatter_apply: null arrays");
   BBGR_REQUIRE(ld_ok(src, ldsrc, d) && ld_ok(dst, lddst, d) && ld_ok(src2, ldsrc2, d),
                "bbgr_scatter_apply: tables must be 16-byte aligned, ld >= d, ld % 4 == 0");
-  const size_t a = align_up(4 * (size_t)n);
-  const char *ws = static_cast<const char *>(plan);
-  const unsigned *k2 = reinterpret_cast<const unsigned *>(ws + a);
-  const int *v2 = reinterpret_cast<const int *>(ws + 3 * a);
+  const ScatterPlan L = scatter_plan_layout(n, n_dst, false);
+  const unsigned *k2 = ws_at<unsigned>(plan, L.k2);
+  const int *v2 = ws_at<int>(plan, L.v2);
   const unsigned grid = (unsigned)((n + 15) / 16);
   for_width(d, [&](auto W) {
     hipLaunchKernelGGL(scatter_segments_kernel<decltype(W)::value>, dim3(grid), dim3(256), 0,
@@ -996,27 +993,20 @@ extern "C" int bbgr_scatter_add_rows(int64_t n, const int64_t *idx, const float 
                                      int64_t ldsrc, float *dst, int64_t lddst, int32_t d,
                                      int64_t n_dst, void *workspace, size_t *workspace_bytes,
                                      bbgr_stream_t stream) {
-  BBGR_REQUIRE(n >= 0 && n < (1ll << 31) && n_dst >= 0 && n_dst < 0xFFFFFFFFll && workspace_bytes,
+  BBGR_REQUIRE(n >= 0 && n < (1ll << 31) && n_dst >= 0 && n_dst < 0xFFFFFFFFll,
                "bbgr_scatter_add_rows: bad sizes");
   if (!supported_width(d)) {
     set_error("bbgr_scatter_add_rows: d = %d unsupported (8, 16, 32, 64, 128, 256)", d);
     return BBGR_ERR_UNSUPPORTED;
   }
-  const size_t need = scatter_plan_bytes(n, n_dst, nullptr, nullptr, as_stream(stream));
-  if (!workspace) {
-    *workspace_bytes = need;
-    return BBGR_OK;
-  }
-  if (*workspace_bytes < need) {
-    set_error("bbgr_scatter_add_rows: workspace %zu < %zu bytes", *workspace_bytes, need);
-    return BBGR_ERR_WORKSPACE;
-  }
-  if (n == 0) return BBGR_OK;
+  bool query;
+  int rc = take_workspace("bbgr_scatter_add_rows", scatter_plan_layout(n, n_dst).total, workspace,
+                          workspace_bytes, &query);
+  if (rc || query || n == 0) return rc;
   BBGR_REQUIRE(idx && src && dst, "bbgr_scatter_add_rows: null arrays");
   BBGR_REQUIRE(ld_ok(src, ldsrc, d) && ld_ok(dst, lddst, d),
                "bbgr_scatter_add_rows: tables must be 16-byte aligned, ld >= d, ld % 4 == 0");
-  size_t have = *workspace_bytes;
-  const int rc = bbgr_scatter_plan(n, idx, n_dst, workspace, &have, stream);
+  rc = bbgr_scatter_plan(n, idx, n_dst, workspace, workspace_bytes, stream);
   if (rc != BBGR_OK) return rc;
   return bbgr_scatter_apply(n, n_dst, workspace, src, ldsrc, nullptr, 0, dst, lddst, d, stream);
 }

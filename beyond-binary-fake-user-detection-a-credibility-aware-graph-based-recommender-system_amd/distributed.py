@@ -584,8 +584,7 @@ class ShardedTrainer(FusedTrainer):
         self._fronts = [_Front(self.B_local, self.B_global, num_local_users, num_items, n_bounds,
                                dev, n_bits) for _ in range(2)]
         self._next = None
-        self._list_ws = None
-        self._list_need = None
+        self._list_ws = _lib.Workspace(grow=False)
         self._use(self._fronts[0])
 
     @classmethod
@@ -752,16 +751,10 @@ class ShardedTrainer(FusedTrainer):
     def _list_rows(self, f: "_Front") -> None:
         st = stream_handle()
         I = self.I
-        if self._list_need is None:   # hipcub's temp size depends on I only
-            need = ctypes.c_size_t(0)
-            call("bbgr_mask_to_list", I, ptr(f.mask_i), ptr(f.item_list), ptr(f.item_count),
-                 None, ctypes.byref(need), st)
-            self._list_need = need.value
-            self._list_ws = torch.empty(max(need.value, 1), dtype=torch.uint8,
-                                        device=self.device)
-        have = ctypes.c_size_t(self._list_ws.numel())
-        call("bbgr_mask_to_list", I, ptr(f.mask_i), ptr(f.item_list), ptr(f.item_count),
-             ptr(self._list_ws), ctypes.byref(have), st)
+        # hipcub's temp size depends on I only: sized by the first call, never asked again
+        _lib.call_with_workspace("bbgr_mask_to_list", I, ptr(f.mask_i), ptr(f.item_list),
+                                 ptr(f.item_count), after=(st,), device=self.device,
+                                 keep=self._list_ws)
         f.rows = self.exchange.list_rows(self.graph.item_csr, f.item_list, f.item_count,
                                          f.offs, f.offs_host, f.positions)
 

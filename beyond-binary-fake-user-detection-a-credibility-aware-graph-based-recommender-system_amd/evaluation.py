@@ -33,7 +33,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import call, ld, ptr, stream_handle
+from ._lib import call, ld, ptr
 from .graph import Csr
 from .sampler import nonempty_rows
 
@@ -162,11 +162,7 @@ def _args(users, train_csr, test_csr, uf, itf, num_items, Ks, pop, total_train, 
 
 
 def _run(fn, a, dev):
-    n = ctypes.c_size_t(0)
-    call(fn, ctypes.byref(a), None, ctypes.byref(n), stream_handle())
-    ws = torch.empty(max(n.value, 1), dtype=torch.uint8, device=dev)
-    call(fn, ctypes.byref(a), ptr(ws), ctypes.byref(n), stream_handle())
-    return ws
+    return _lib.call_with_workspace(fn, ctypes.byref(a), device=dev)
 
 
 def _results(sums, Ks, num_items, cred_utility, mode, extra):

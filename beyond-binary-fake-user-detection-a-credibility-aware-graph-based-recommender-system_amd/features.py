@@ -166,11 +166,8 @@ def _csr_build(rows: torch.Tensor, cols: torch.Tensor, n_rows: int, n_cols: int,
     E = rows.numel()
     indptr = torch.empty(n_rows + 1, dtype=torch.int32, device=dev)
     indices = torch.empty(max(E, 1), dtype=torch.int32, device=dev)
-    st = stream_handle()
-    args = (E, ptr(rows), ptr(cols), n_rows, n_cols, ptr(indptr), ptr(indices), ptr(perm))
-    nb = _lib.workspace_query("bbgr_csr_build", *args, args_after=(st,))
-    ws = torch.empty(max(nb, 1), dtype=torch.uint8, device=dev)
-    call("bbgr_csr_build", *args, ptr(ws), ctypes.byref(ctypes.c_size_t(nb)), st)
+    _lib.call_with_workspace("bbgr_csr_build", E, ptr(rows), ptr(cols), n_rows, n_cols,
+                             ptr(indptr), ptr(indices), ptr(perm), device=dev)
     return indptr, indices
 
 
@@ -181,15 +178,6 @@ def _group(ids: torch.Tensor, zeros: torch.Tensor, n_rows: int):
     eid = torch.empty(max(ids.numel(), 1), dtype=torch.int32, device=ids.device)
     indptr, _ = _csr_build(ids, zeros, n_rows, 1, perm=eid)
     return indptr, eid
-
-
-def _with_workspace(fn: str, *args) -> None:
-    """Call an entry point whose last arguments are (workspace, &bytes, stream)."""
-    st = stream_handle()
-    nb = _lib.workspace_query(fn, *args, args_after=(st,))
-    dev = torch.device("cuda", torch.cuda.current_device())
-    ws = torch.empty(max(nb, 1), dtype=torch.uint8, device=dev)
-    call(fn, *args, ptr(ws), ctypes.byref(ctypes.c_size_t(nb)), st)
 
 
 def build_credibility_graph(cols: ReviewColumns, num_users: int, num_items: int,
@@ -316,8 +304,9 @@ class _Pipeline:
                                                   self.n_bucket_cols)
 
     def items(self) -> None:
-        _with_workspace("bbgr_feat_items", self.cref, ptr(self.i_indptr), ptr(self.i_eid),
-                        ptr(self.item_x), ptr(self.item_rbar))
+        _lib.call_with_workspace("bbgr_feat_items", self.cref, ptr(self.i_indptr),
+                                 ptr(self.i_eid), ptr(self.item_x), ptr(self.item_rbar),
+                                 device=self.dev)
 
     def users(self) -> None:
         a = _lib.FeatUserArgs()
@@ -326,7 +315,7 @@ class _Pipeline:
         a.item_rbar, a.global_avg_len = ptr(self.item_rbar), self.global_avg_len
         a.user_x, a.user_y = ptr(self.user_x), ptr(self.user_y)
         a.total_reviews, a.helpful_reviews = ptr(self.total), ptr(self.helpful_reviews)
-        _with_workspace("bbgr_feat_users", self.cref, ctypes.byref(a))
+        _lib.call_with_workspace("bbgr_feat_users", self.cref, ctypes.byref(a), device=self.dev)
 
     def edges(self) -> None:
         call("bbgr_feat_edges", self.cref, ptr(self.item_x), self.ts_min, self.ts_max,
@@ -362,7 +351,8 @@ class _PipelineV2(_Pipeline):
 
     def stats(self) -> None:
         super().stats()
-        _with_workspace("bbgr_feat_lenlog", self.cref, ptr(self.lenlog_dev))
+        _lib.call_with_workspace("bbgr_feat_lenlog", self.cref, ptr(self.lenlog_dev),
+                                 device=self.dev)
 
     def read_stats(self) -> None:
         """The one host read: four integers and the sum of log1p(n_tokens)."""
@@ -371,8 +361,8 @@ class _PipelineV2(_Pipeline):
 
     def items(self) -> None:
         super().items()
-        _with_workspace("bbgr_feat_item_means", self.cref, ptr(self.i_indptr), ptr(self.i_eid),
-                        ptr(self.item_mean))
+        _lib.call_with_workspace("bbgr_feat_item_means", self.cref, ptr(self.i_indptr),
+                                 ptr(self.i_eid), ptr(self.item_mean), device=self.dev)
 
     def pooled(self) -> None:
         from .text import pooled_token_counts
@@ -380,8 +370,8 @@ class _PipelineV2(_Pipeline):
             self.text, self.user, self.U, self.dev)
 
     def gaps(self) -> None:
-        _with_workspace("bbgr_feat_gaps", self.cref, ptr(self.u_indptr), ptr(self.u_eid),
-                        ptr(self.etg))
+        _lib.call_with_workspace("bbgr_feat_gaps", self.cref, ptr(self.u_indptr),
+                                 ptr(self.u_eid), ptr(self.etg), device=self.dev)
 
     def users(self) -> None:
         a = _lib.FeatUserV2Args()
@@ -393,7 +383,8 @@ class _PipelineV2(_Pipeline):
         a.user_x, a.user_y = ptr(self.user_x), ptr(self.user_y)
         a.total_reviews, a.helpful_reviews = ptr(self.total), ptr(self.helpful_reviews)
         a.user_extra = ptr(self.user_extra)
-        _with_workspace("bbgr_feat_users_v2", self.cref, ctypes.byref(a))
+        _lib.call_with_workspace("bbgr_feat_users_v2", self.cref, ctypes.byref(a),
+                                 device=self.dev)
 
     STEPS = ("stats", "read_stats", "buckets", "group_users", "group_items", "group_buckets",
              "items", "pooled", "gaps", "users", "edges")

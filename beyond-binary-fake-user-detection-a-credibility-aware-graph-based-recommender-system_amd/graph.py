@@ -99,15 +99,9 @@ class Csr:
         self.indices = torch.empty(max(nnz, 1), dtype=torch.int32, device=device)
         perm = (torch.empty(max(nnz, 1), dtype=torch.int32, device=device)
                 if edge_values is not None or keep_perm else None)
-        st = stream_handle()
-        ws_bytes = _lib.workspace_query(
-            "bbgr_csr_build", nnz, ptr(rows), ptr(cols), self.n_rows, self.n_cols,
-            ptr(self.indptr), ptr(self.indices), ptr(perm), args_after=(st,))
-        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=device)
-        n = ctypes.c_size_t(ws_bytes)
-        call("bbgr_csr_build", nnz, ptr(rows), ptr(cols), self.n_rows, self.n_cols,
-             ptr(self.indptr), ptr(self.indices), ptr(perm), ptr(ws), ctypes.byref(n), st)
-        del ws
+        _lib.call_with_workspace("bbgr_csr_build", nnz, ptr(rows), ptr(cols), self.n_rows,
+                                 self.n_cols, ptr(self.indptr), ptr(self.indices), ptr(perm),
+                                 device=device)
         self.perm = perm if keep_perm else None   # CSR slot -> input edge id
         self.values = None
         if edge_values is not None:
@@ -119,14 +113,10 @@ class Csr:
         s = self.struct(with_plan=False)
         s.long_threshold = long_threshold
         s.chunk_edges = chunk_edges
-        st = stream_handle()
-        ws_bytes = _lib.workspace_query("bbgr_csr_plan_count", ctypes.byref(s), None,
-                                        None, args_after=(st,))
-        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=self.device)
-        nb = ctypes.c_size_t(ws_bytes)
         nc, ns = ctypes.c_int32(0), ctypes.c_int32(0)
-        call("bbgr_csr_plan_count", ctypes.byref(s), ctypes.byref(nc), ctypes.byref(ns),
-             ptr(ws), ctypes.byref(nb), st)
+        keep = _lib.Workspace(grow=False)   # the count and the build share one buffer
+        _lib.call_with_workspace("bbgr_csr_plan_count", ctypes.byref(s), ctypes.byref(nc),
+                                 ctypes.byref(ns), device=self.device, keep=keep)
         self.long_threshold, self.chunk_edges = long_threshold, chunk_edges
         self.n_chunks, self.n_split = nc.value, ns.value
         self.chunks = torch.empty(max(4 * self.n_chunks, 4), dtype=torch.int32,
@@ -134,8 +124,8 @@ class Csr:
         self.split = torch.empty(max(4 * self.n_split, 4), dtype=torch.int32,
                                  device=self.device)
         s.n_chunks, s.n_split = self.n_chunks, self.n_split
-        call("bbgr_csr_plan_build", ctypes.byref(s), ptr(self.chunks), ptr(self.split),
-             ptr(ws), ctypes.byref(nb), st)
+        _lib.call_with_workspace("bbgr_csr_plan_build", ctypes.byref(s), ptr(self.chunks),
+                                 ptr(self.split), keep=keep)
         self._struct = self.struct(with_plan=True)
 
     def struct(self, with_plan: bool = True) -> _lib.CsrStruct:
@@ -251,13 +241,8 @@ class VertexOrder:
         dev = degree.device
         self.perm = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
         self.rank = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
-        st = stream_handle()
-        nb = _lib.workspace_query("bbgr_degree_order", n, ptr(degree), ptr(self.perm),
-                                  ptr(self.rank), args_after=(st,))
-        ws = torch.empty(max(nb, 1), dtype=torch.uint8, device=dev)
-        have = ctypes.c_size_t(nb)
-        call("bbgr_degree_order", n, ptr(degree), ptr(self.perm), ptr(self.rank), ptr(ws),
-             ctypes.byref(have), st)
+        _lib.call_with_workspace("bbgr_degree_order", n, ptr(degree), ptr(self.perm),
+                                 ptr(self.rank), device=dev)
         self.perm, self.rank = self.perm[:n], self.rank[:n]
         self._perm64 = self.perm.long()
         self._rank64 = self.rank.long()
@@ -282,13 +267,8 @@ class VertexOrder:
 def _degree_count(ids: torch.Tensor, n: int) -> torch.Tensor:
     """Exact occurrence counts (bbgr_degree_count_ws: per-XCD counter copies)."""
     deg = torch.empty(max(n, 1), dtype=torch.int32, device=ids.device)
-    st = stream_handle()
-    nb = _lib.workspace_query("bbgr_degree_count_ws", ids.numel(), ptr(ids), n, ptr(deg),
-                              args_after=(st,))
-    ws = torch.empty(max(nb, 1), dtype=torch.uint8, device=ids.device)
-    have = ctypes.c_size_t(nb)
-    call("bbgr_degree_count_ws", ids.numel(), ptr(ids), n, ptr(deg), ptr(ws),
-         ctypes.byref(have), st)
+    _lib.call_with_workspace("bbgr_degree_count_ws", ids.numel(), ptr(ids), n, ptr(deg),
+                             device=ids.device)
     return deg[:n]
 
 

@@ -193,13 +193,6 @@ def host_record(raw: bytes, item_id_key: str):
             s.encode("utf-8", "surrogatepass"))
 
 
-def _with_workspace(fn: str, dev, *args) -> None:
-    st = stream_handle()
-    nb = _lib.workspace_query(fn, *args, args_after=(st,))
-    ws = torch.empty(max(nb, 1), dtype=torch.uint8, device=dev)
-    call(fn, *args, ptr(ws), ctypes.byref(ctypes.c_size_t(nb)), st)
-
-
 class _Chunk(NamedTuple):
     """The compact outputs of one chunk (device tensors; offsets [records])."""
     rating: torch.Tensor
@@ -239,7 +232,7 @@ class _Reader:
         n = self.n_lines
         self.line_end = torch.empty(max(n, 1), dtype=torch.int32, device=self.dev)
         self.a.line_end = ptr(self.line_end)
-        _with_workspace("bbgr_jsonl_lines", self.dev, self.ref)
+        _lib.call_with_workspace("bbgr_jsonl_lines", self.ref, device=self.dev)
 
     def scan(self) -> None:
         n, dev, a = max(self.n_lines, 1), self.dev, self.a
@@ -325,7 +318,7 @@ class _Reader:
     def offsets(self) -> None:
         self.offs = torch.empty((4, self.n_lines + 1), dtype=torch.int64, device=self.dev)
         self.a.offs = ptr(self.offs)
-        _with_workspace("bbgr_jsonl_offsets", self.dev, self.ref)
+        _lib.call_with_workspace("bbgr_jsonl_offsets", self.ref, device=self.dev)
 
     def read_offsets(self) -> None:
         a = self.a
@@ -409,17 +402,17 @@ def number_ids(data: torch.Tensor, off: torch.Tensor, hash_mask: int = 0):
     ids = torch.empty(n, dtype=torch.int32, device=dev)
     first_rec = torch.empty(n, dtype=torch.int32, device=dev)
     totals = torch.zeros(2, dtype=torch.int64, device=dev)
-    _with_workspace("bbgr_ids_number", dev, n, ptr(d), ptr(off), data.numel(), int(hash_mask),
-                    ptr(ids), ptr(first_rec), ptr(totals))
+    _lib.call_with_workspace("bbgr_ids_number", n, ptr(d), ptr(off), data.numel(), int(hash_mask),
+                             ptr(ids), ptr(first_rec), ptr(totals), device=dev)
     n_ids, collisions = (int(v) for v in totals.tolist())
     if collisions:
         return (*_number_on_host(data, off, dev), True)
     tab_off = torch.empty(n_ids + 1, dtype=torch.int64, device=dev)
     args = (n_ids, ptr(first_rec), n, ptr(d), ptr(off), data.numel(), ptr(tab_off))
-    _with_workspace("bbgr_ids_table", dev, *args, None, 0)
+    _lib.call_with_workspace("bbgr_ids_table", *args, None, 0, device=dev)
     tab_bytes = int(tab_off[-1])
     tab = torch.empty(max(tab_bytes, 1), dtype=torch.uint8, device=dev)
-    _with_workspace("bbgr_ids_table", dev, *args, ptr(tab), tab_bytes)
+    _lib.call_with_workspace("bbgr_ids_table", *args, ptr(tab), tab_bytes, device=dev)
     return ids, IdTable(tab[:tab_bytes], tab_off), False
 
 

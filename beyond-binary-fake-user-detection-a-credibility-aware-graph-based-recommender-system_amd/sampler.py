@@ -17,8 +17,6 @@ reproduced ("Sampler parity").
 """
 from __future__ import annotations
 
-import ctypes
-
 import torch
 
 from . import _lib
@@ -50,13 +48,8 @@ class PopMixSampler:
             if item_csr is None:
                 raise ValueError("pop-mix sampling needs the item-row CSR (item degrees)")
             self.cdf = torch.empty(self.num_items, dtype=torch.float64, device=user_csr.device)
-            st = stream_handle()
-            nb = _lib.workspace_query("bbgr_pop_cdf", self.num_items, ptr(item_csr.indptr),
-                                      float(gamma), ptr(self.cdf), args_after=(st,))
-            ws = torch.empty(max(nb, 1), dtype=torch.uint8, device=user_csr.device)
-            n = ctypes.c_size_t(nb)
-            call("bbgr_pop_cdf", self.num_items, ptr(item_csr.indptr), float(gamma),
-                 ptr(self.cdf), ptr(ws), ctypes.byref(n), st)
+            _lib.call_with_workspace("bbgr_pop_cdf", self.num_items, ptr(item_csr.indptr),
+                                     float(gamma), ptr(self.cdf), device=user_csr.device)
 
     def sample(self, users: torch.Tensor, pos: torch.Tensor | None = None,
                neg: torch.Tensor | None = None, counter: int | None = None,
@@ -88,24 +81,15 @@ def shuffle(values: torch.Tensor, seed: int, counter: int, out: torch.Tensor | N
     values = values.to(dtype=torch.int64).contiguous()
     n = values.numel()
     out = torch.empty_like(values) if out is None else out
-    st = stream_handle()
-    nb = _lib.workspace_query("bbgr_shuffle", n, ptr(values), ptr(out), seed, counter,
-                              args_after=(st,))
-    ws = torch.empty(max(nb, 1), dtype=torch.uint8, device=values.device)
-    b = ctypes.c_size_t(nb)
-    call("bbgr_shuffle", n, ptr(values), ptr(out), seed, counter, ptr(ws), ctypes.byref(b), st)
+    _lib.call_with_workspace("bbgr_shuffle", n, ptr(values), ptr(out), seed, counter,
+                             device=values.device)
     return out
 
 
 def nonempty_rows(csr: Csr) -> torch.Tensor:
     """Rows with >= 1 edge, ascending (train_users, Version-2:797-798)."""
-    st = stream_handle()
     out = torch.empty(max(csr.n_rows, 1), dtype=torch.int64, device=csr.device)
     count = torch.zeros(1, dtype=torch.int64, device=csr.device)
-    nb = _lib.workspace_query("bbgr_nonempty_rows", csr.n_rows, ptr(csr.indptr), ptr(out),
-                              ptr(count), args_after=(st,))
-    ws = torch.empty(max(nb, 1), dtype=torch.uint8, device=csr.device)
-    b = ctypes.c_size_t(nb)
-    call("bbgr_nonempty_rows", csr.n_rows, ptr(csr.indptr), ptr(out), ptr(count), ptr(ws),
-         ctypes.byref(b), st)
+    _lib.call_with_workspace("bbgr_nonempty_rows", csr.n_rows, ptr(csr.indptr), ptr(out),
+                             ptr(count), device=csr.device)
     return out[: int(count.item())]

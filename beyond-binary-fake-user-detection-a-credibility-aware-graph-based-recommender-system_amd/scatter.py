@@ -9,8 +9,6 @@ results are bitwise reproducible.
 """
 from __future__ import annotations
 
-import ctypes
-
 import torch
 
 from . import _lib
@@ -21,7 +19,7 @@ class RowScatter:
     """Reusable workspace for bbgr_scatter_add_rows (grown on demand)."""
 
     def __init__(self):
-        self._ws = None
+        self._ws = _lib.Workspace()
 
     def __call__(self, dst: torch.Tensor, index: torch.Tensor, src: torch.Tensor,
                  unique: bool = False) -> torch.Tensor:
@@ -40,13 +38,9 @@ class RowScatter:
             call("bbgr_rows_add_unique", n, ptr(index), ptr(src), ld(src), ptr(dst), ld(dst),
                  dst.shape[1], dst.shape[0], stream_handle())
             return dst
-        need = ctypes.c_size_t(0)
-        args = (n, ptr(index), ptr(src), ld(src), ptr(dst), ld(dst), dst.shape[1], dst.shape[0])
-        call("bbgr_scatter_add_rows", *args, None, ctypes.byref(need), stream_handle())
-        if self._ws is None or self._ws.numel() < need.value:
-            self._ws = torch.empty(max(need.value, 1), dtype=torch.uint8, device=dst.device)
-        have = ctypes.c_size_t(self._ws.numel())
-        call("bbgr_scatter_add_rows", *args, ptr(self._ws), ctypes.byref(have), stream_handle())
+        _lib.call_with_workspace("bbgr_scatter_add_rows", n, ptr(index), ptr(src), ld(src),
+                                 ptr(dst), ld(dst), dst.shape[1], dst.shape[0],
+                                 device=dst.device, keep=self._ws)
         return dst
 
 

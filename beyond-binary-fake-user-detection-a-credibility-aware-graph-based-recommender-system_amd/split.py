@@ -234,10 +234,7 @@ def _run_split(user, item, positive, rating, pos_threshold: float, hash_raw, thr
     a.user_map, a.item_map = ptr(user_map), ptr(item_map)
     a.user_src, a.item_src = ptr(user_src), ptr(item_src)
     a.edges, a.ld_edges, a.counts = ptr(edges), edges.stride(0), ptr(counts)
-    st = stream_handle()
-    nb = _lib.workspace_query("bbgr_split_edges", ctypes.byref(a), args_after=(st,))
-    ws = torch.empty(max(nb, 1), dtype=torch.uint8, device=user.device)
-    call("bbgr_split_edges", ctypes.byref(a), ptr(ws), ctypes.byref(ctypes.c_size_t(nb)), st)
+    _lib.call_with_workspace("bbgr_split_edges", ctypes.byref(a), device=user.device)
 
 
 def split_interactions(user, item, rating, user_ids: IdTable, item_ids: IdTable, *,

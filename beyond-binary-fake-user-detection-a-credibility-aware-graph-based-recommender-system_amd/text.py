@@ -165,10 +165,8 @@ def _run_chunk(data: torch.Tensor, off: torch.Tensor, first: int, last: int, has
     st = stream_handle()
     call("bbgr_text_count", ctypes.byref(a), st)
     tokens = int(totals[0])                                  # the host read that sizes the workspace
-    nb = _lib.workspace_query("bbgr_text_unique", ctypes.byref(a), tokens, args_after=(st,))
-    ws = torch.empty(max(nb, 1), dtype=torch.uint8, device=data.device)
-    call("bbgr_text_unique", ctypes.byref(a), tokens, ptr(ws), ctypes.byref(ctypes.c_size_t(nb)),
-         st)
+    _lib.call_with_workspace("bbgr_text_unique", ctypes.byref(a), tokens, after=(st,),
+                             device=data.device)
     return tokens, int(totals[1])
 
 
@@ -294,10 +292,8 @@ def pooled_token_counts(text: ReviewText, group, num_groups: int, device="cuda",
         st = stream_handle()
         call("bbgr_text_count", ctypes.byref(a), st)
         tokens = int(totals[0])                                  # sizes the workspace
-        args = (ctypes.byref(a), tokens, ptr(grp), G, ptr(g_tok), ptr(g_uniq), ptr(g_flag))
-        nb = _lib.workspace_query("bbgr_text_unique_pooled", *args, args_after=(st,))
-        ws = torch.empty(max(nb, 1), dtype=torch.uint8, device=dev)
-        call("bbgr_text_unique_pooled", *args, ptr(ws), ctypes.byref(ctypes.c_size_t(nb)), st)
+        _lib.call_with_workspace("bbgr_text_unique_pooled", ctypes.byref(a), tokens, ptr(grp), G,
+                                 ptr(g_tok), ptr(g_uniq), ptr(g_flag), after=(st,), device=dev)
         flagged = int(totals[1])
         if flagged:
             idx = torch.nonzero(g_flag).flatten()

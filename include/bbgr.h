@@ -6,8 +6,13 @@
  *
  * Conventions (every entry point):
  *   - Caller-owned DEVICE buffers; no allocation inside hot calls. Entry points that
- *     need scratch take (workspace, workspace_bytes); call them once with
- *     workspace == NULL to query the size.
+ *     need scratch take (workspace, workspace_bytes), all by one protocol:
+ *     workspace == NULL queries the size into *workspace_bytes (nothing is
+ *     launched); a workspace of fewer than that many bytes is refused with
+ *     BBGR_ERR_WORKSPACE and the text "<entry>: workspace <have> < <need>
+ *     bytes"; a null workspace_bytes is BBGR_ERR_INVALID. A size query may need
+ *     a device: where hipcub sizes its own temporary storage (scans, selects,
+ *     the larger sorts) it asks the runtime for one.
  *   - Stream-ordered on the hipStream_t passed as `stream` (NULL = default stream).
  *     No host synchronisation except in the entry points documented as "syncs"
  *     (one-time operator planning only).

@@ -187,13 +187,14 @@ def pooled_main(args):
     tokens = int(totals[0])
     head = (ctypes.byref(a), tokens, _lib.ptr(grp), U, _lib.ptr(g_tok), _lib.ptr(g_uniq),
             _lib.ptr(g_flag))
-    nb = _lib.workspace_query("bbgr_text_unique_pooled", *head, args_after=(st,))
-    ws = torch.empty(nb, dtype=torch.uint8, device=dev)
-    rec.update(device_tokens=tokens, workspace_bytes=nb)
+    # one whole call sizes the workspace the launch groups below run on
+    keep = _lib.Workspace(grow=False)
+    _lib.call_with_workspace("bbgr_text_unique_pooled", *head, after=(st,), device=dev, keep=keep)
+    rec.update(device_tokens=tokens, workspace_bytes=keep.buf.numel())
 
     def stage(bits):
-        return lambda: _lib.call("bbgr_text_unique_pooled_stages", *head, bits, _lib.ptr(ws),
-                                 ctypes.byref(ctypes.c_size_t(nb)), st)
+        return lambda: _lib.call_with_workspace("bbgr_text_unique_pooled_stages", *head, bits,
+                                                after=(st,), keep=keep)
 
     kernels = {name: timed_events(stage(bits), args.warmup, args.reps)
                for name, bits in (("emit", 1), ("sort", 2), ("verify", 4))}
@@ -203,7 +204,7 @@ def pooled_main(args):
     rec["kernels"] = kernels
     rec["kernels_sum_ms"] = sum(r["median_ms"] for r in kernels.values())
     rec["flagged_groups"] = int(totals[1])
-    del ws
+    del keep
     ts = []
     for k in range(args.warmup + args.reps):
         torch.cuda.synchronize()
@@ -292,13 +293,16 @@ def main():
     st = _lib.stream_handle()
     _lib.call("bbgr_text_count", ctypes.byref(a), st)
     tokens = int(totals[0])
-    nb = _lib.workspace_query("bbgr_text_unique", ctypes.byref(a), tokens, args_after=(st,))
-    ws = torch.empty(nb, dtype=torch.uint8, device=dev)
-    rec.update(device_tokens=tokens, tokens_per_record=tokens / max(n, 1), workspace_bytes=nb)
+    # one whole call sizes the workspace the launch groups below run on
+    keep = _lib.Workspace(grow=False)
+    _lib.call_with_workspace("bbgr_text_unique", ctypes.byref(a), tokens, after=(st,), device=dev,
+                             keep=keep)
+    rec.update(device_tokens=tokens, tokens_per_record=tokens / max(n, 1),
+               workspace_bytes=keep.buf.numel())
 
     def stage(bits):
-        return lambda: _lib.call("bbgr_text_unique_stages", ctypes.byref(a), tokens, bits,
-                                 _lib.ptr(ws), ctypes.byref(ctypes.c_size_t(nb)), st)
+        return lambda: _lib.call_with_workspace("bbgr_text_unique_stages", ctypes.byref(a), tokens,
+                                                bits, after=(st,), keep=keep)
 
     groups = {"count": lambda: _lib.call("bbgr_text_count", ctypes.byref(a), st),
               "emit": stage(1), "sort": stage(2), "verify": stage(4)}
@@ -312,7 +316,7 @@ def main():
     rec["kernels"] = kernels
     rec["kernels_sum_ms"] = sum(r["median_ms"] for r in kernels.values())
     rec["sort_share"] = kernels["sort"]["median_ms"] / rec["kernels_sum_ms"]
-    del ws
+    del keep
 
     ts = []
     for k in range(args.warmup + args.reps):
