@@ -249,6 +249,19 @@ class TextArgs(ctypes.Structure):
     ]
 
 
+TEXT_FETCH = {"unaligned": 0, "aligned_pair": 1}   # BBGR_TEXT_FETCH_*
+
+
+class TextGatherArgs(ctypes.Structure):
+    """bbgr_text_gather_args (bbgr_text_gather, bbgr_text_gather_fetch)."""
+    _fields_ = [
+        ("n_list", c_int64), ("records", c_void_p), ("n", c_int64), ("data", c_void_p),
+        ("offsets", c_void_p), ("first", c_int64), ("last", c_int64),
+        ("out_offsets", c_void_p), ("out_data", c_void_p), ("capacity", c_int64),
+        ("total", c_void_p),
+    ]
+
+
 class JsonlArgs(ctypes.Structure):
     """bbgr_jsonl_args (bbgr_jsonl_count .. bbgr_jsonl_write)."""
     _fields_ = [
@@ -436,6 +449,10 @@ _SIGNATURES = {
                                  ctypes.POINTER(c_size_t), _P], c_int32),
     "bbgr_text_unique_pooled_stages": ([ctypes.POINTER(TextArgs), c_int64, _P, c_int32, _P, _P, _P,
                                         c_int32, _P, ctypes.POINTER(c_size_t), _P], c_int32),
+    "bbgr_text_gather": ([ctypes.POINTER(TextGatherArgs), _P, ctypes.POINTER(c_size_t), _P],
+                         c_int32),
+    "bbgr_text_gather_fetch": ([ctypes.POINTER(TextGatherArgs), c_int32, _P,
+                                ctypes.POINTER(c_size_t), _P], c_int32),
     "bbgr_feat_lenlog": ([ctypes.POINTER(FeatColumns), _P, _P, ctypes.POINTER(c_size_t), _P],
                          c_int32),
     "bbgr_feat_item_means": ([ctypes.POINTER(FeatColumns), _P, _P, _P, _P,

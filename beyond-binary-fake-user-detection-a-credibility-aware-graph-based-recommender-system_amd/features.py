@@ -33,11 +33,13 @@ atomics: two calls give the same bits.
 same graph pass and model: columns 3 to 6 in its definitions (deviation from
 the item mean of the raw rating, the burst count over n, POOLED lexical
 diversity, the discrepancy of ``log1p`` lengths) and ``user_extra`` = (RNR,
-ETG) beside them. It needs ``cols.text`` (resident as one chunk, below
-2^31 - 1 bytes: ``bbgr.text.pooled_token_counts``; users it flags are counted
-again on the host) and adds ``bbgr_feat_lenlog``, ``bbgr_feat_item_means``,
-``bbgr_text_unique_pooled``, ``bbgr_feat_gaps`` and ``bbgr_feat_users_v2`` in
-``bbgr_feat_users``' place.
+ETG) beside them. It needs ``cols.text`` (``bbgr.text.pooled_token_counts``:
+by default resident as one chunk, below 2^31 - 1 bytes; with
+``text_chunk_bytes`` of any size that fits the device beside one chunk,
+regrouped by user with ``bbgr_text_gather`` into chunks of whole users, the
+same bits; users it flags are counted again on the host) and adds
+``bbgr_feat_lenlog``, ``bbgr_feat_item_means``, ``bbgr_text_unique_pooled``,
+``bbgr_feat_gaps`` and ``bbgr_feat_users_v2`` in ``bbgr_feat_users``' place.
 """
 from __future__ import annotations
 
@@ -181,7 +183,7 @@ def _group(ids: torch.Tensor, zeros: torch.Tensor, n_rows: int):
 
 
 def build_credibility_graph(cols: ReviewColumns, num_users: int, num_items: int,
-                            device="cuda", feature_set: str = "main"):
+                            device="cuda", feature_set: str = "main", text_chunk_bytes=None):
     """Labels, user and item features and edge attributes of the records in
     `cols` (module docstring). Raises ValueError, before any launch, for an id
     outside [0, num_users) / [0, num_items) or E >= 2^31 - 1, and
@@ -195,7 +197,13 @@ def build_credibility_graph(cols: ReviewColumns, num_users: int, num_items: int,
     ``feature_set="main"`` returns a ``CredibilityGraph``; ``"v2"`` (module
     docstring) a ``CredibilityGraphV2`` and needs ``cols.text``: ValueError
     naming text without it, or for text of 2^31 - 1 bytes or more; ``n_tokens``
-    is taken from the columns when given, else counted."""
+    is taken from the columns when given, else counted.
+    ``text_chunk_bytes=<int>`` ("v2"; accepted and unused by "main") lifts that
+    limit: the text goes to the device once, ``token_counts`` and the pooled
+    count both read it there, and the pooled count regroups it by user into
+    chunks of at most that many bytes (``pooled_token_counts(.., chunk_bytes)``)
+    over the user rows this build groups anyway. The same tensors come back.
+    A record and a user's text stay below 2^31 - 1 bytes each."""
     device = torch.device(device)
     if device.type != "cuda":
         raise ValueError("build_credibility_graph runs on the GPU; there is no CPU fallback")
@@ -210,8 +218,10 @@ def build_credibility_graph(cols: ReviewColumns, num_users: int, num_items: int,
                              "cannot be made from two integers per record")
         if len(cols.text) != E:
             raise ValueError(f"text: expected {E} records, got {len(cols.text)}")
+        if text_chunk_bytes is not None and int(text_chunk_bytes) < 1:
+            raise ValueError("text_chunk_bytes must be at least 1")
         span = int(cols.text.offsets[-1]) - int(cols.text.offsets[0])
-        if span >= BYTES_MAX:
+        if text_chunk_bytes is None and span >= BYTES_MAX:
             raise ValueError(f"text of {span} bytes: feature_set='v2' takes the text as one "
                              "chunk, which must be shorter than 2^31 - 1 bytes")
     elif cols.n_tokens is None or cols.n_unique_tokens is None:
@@ -227,6 +237,9 @@ def build_credibility_graph(cols: ReviewColumns, num_users: int, num_items: int,
         _check_ids(cols.user, "user", U, "num_users")
         _check_ids(cols.item, "item", I, "num_items")
     _lib.require_gpu()
+    if v2 and text_chunk_bytes is not None:
+        from .text import resident
+        cols = dataclasses.replace(cols, text=resident(cols.text, device))   # the one upload
     if v2 and cols.n_tokens is not None:
         if cols.n_unique_tokens is None:     # not read by the v2 pass; the columns struct wants one
             cols = dataclasses.replace(cols, n_unique_tokens=cols.n_tokens)
@@ -236,7 +249,9 @@ def build_credibility_graph(cols: ReviewColumns, num_users: int, num_items: int,
         cols = dataclasses.replace(cols, n_tokens=n_tok, n_unique_tokens=n_uniq)
     with torch.cuda.device(device):
         dev = torch.device("cuda", torch.cuda.current_device())
-        return (_PipelineV2 if v2 else _Pipeline)(cols, U, I, E, dev).run()
+        if not v2:
+            return _Pipeline(cols, U, I, E, dev).run()
+        return _PipelineV2(cols, U, I, E, dev, text_chunk_bytes).run()
 
 
 class _Pipeline:
@@ -340,9 +355,10 @@ class _PipelineV2(_Pipeline):
     them, the pooled count and the gap entropy before the user pass, and
     ``bbgr_feat_users_v2`` as the user pass."""
 
-    def __init__(self, cols: ReviewColumns, U: int, I: int, E: int, dev):
+    def __init__(self, cols: ReviewColumns, U: int, I: int, E: int, dev, text_chunk_bytes=None):
         super().__init__(cols, U, I, E, dev)
         self.text = cols.text
+        self.text_chunk_bytes = text_chunk_bytes
         f64 = dict(dtype=torch.float64, device=dev)
         self.lenlog_dev = torch.empty(1, **f64)
         self.item_mean = torch.empty(max(I, 1), **f64)
@@ -366,8 +382,14 @@ class _PipelineV2(_Pipeline):
 
     def pooled(self) -> None:
         from .text import pooled_token_counts
+        if self.text_chunk_bytes is None:
+            self.group_tokens, self.group_unique, self.pooled_info = pooled_token_counts(
+                self.text, self.user, self.U, self.dev)
+            return
+        # regrouped by user, over the user rows group_users has built
         self.group_tokens, self.group_unique, self.pooled_info = pooled_token_counts(
-            self.text, self.user, self.U, self.dev)
+            self.text, self.user, self.U, self.dev, chunk_bytes=self.text_chunk_bytes,
+            group_csr=(self.u_indptr, self.u_eid))
 
     def gaps(self) -> None:
         _lib.call_with_workspace("bbgr_feat_gaps", self.cref, ptr(self.u_indptr),

@@ -1474,7 +1474,12 @@ int bbgr_text_unique_stages(const bbgr_text_args *args, int64_t total_tokens, in
 /* where the group or the hash differs from the left neighbour's, and with     */
 /* both equal a comparison of the two tokens' normalised bytes and lengths. An */
 /* unflagged group's count is therefore exact. total_tokens as for             */
-/* bbgr_text_unique; the text is one chunk (last - first < 2^31 - 1 bytes).    */
+/* bbgr_text_unique; one call takes last - first < 2^31 - 1 bytes. Equal       */
+/* tokens only have to meet inside a group, so longer text is counted in       */
+/* several calls, each on whole groups packed back to back by bbgr_text_gather */
+/* with group ids local to the call: every output depends on the multiset of a */
+/* group's tokens alone, not on the order of its records, and so equals the    */
+/* one-call result bit for bit (bbgr.text.pooled_token_counts, chunk_bytes).   */
 /* The workspace holds 40 bytes per token, 4 per record and the sorts' own.    */
 /* Size query with workspace == NULL; stream-ordered, no synchronisation.      */
 int bbgr_text_unique_pooled(const bbgr_text_args *args, int64_t total_tokens,
@@ -1665,6 +1670,46 @@ int bbgr_ids_table(int64_t n_ids, const int32_t *first_rec, int64_t n, const uin
                    const int64_t *offsets, int64_t data_bytes, int64_t *tab_offsets,
                    uint8_t *tab_data, int64_t tab_bytes, void *workspace, size_t *workspace_bytes,
                    bbgr_stream_t stream);
+
+/* ------------------------------------------------------------------------- */
+/* Pack listed records of a text of any size back to back (bbgr.text regroups  */
+/* the records by user with it, so that a chunk of bbgr_text_unique_pooled     */
+/* holds whole users). Appended; the ABI stays 12.                             */
+/* ------------------------------------------------------------------------- */
+typedef struct {
+  int64_t n_list;          /* listed records, < 2^31 - 1 */
+  const int32_t *records;  /* DEVICE [n_list]: record ids; one outside [0, n) has length 0 */
+  int64_t n;               /* records of the source text */
+  const uint8_t *data;     /* DEVICE: source bytes, ANY size (64-bit addressing) */
+  const int64_t *offsets;  /* DEVICE [n + 1], clamped into [first, last] as bbgr_text_args does */
+  int64_t first, last;     /* HOST; last - first is NOT limited here */
+  int64_t *out_offsets;    /* DEVICE [n_list + 1]: 0, then the running sum of the lengths */
+  uint8_t *out_data;       /* DEVICE [capacity], 16-byte aligned; NULL: offsets and total only */
+  int64_t capacity;
+  int64_t *total;          /* DEVICE int64 [1] = out_offsets[n_list] */
+} bbgr_text_gather_args;
+/* Listed record j is copied to out_data[out_offsets[j], out_offsets[j + 1]);  */
+/* ids may repeat and come in any order, records may be empty. No byte at or   */
+/* beyond min(total, capacity) is written and no address outside               */
+/* data[first, last) is loaded. One lane per listed record takes its clamped   */
+/* length, hipcub scans the lengths, and the copy is output-centric: a wave    */
+/* owns 1 KiB of the packed bytes at a time, finds the records that touch it   */
+/* in out_offsets, and each lane assembles one aligned 16-byte word (from one  */
+/* unaligned 16-byte load where the word lies in one record). Plain copies:    */
+/* two calls give the same bytes. The workspace holds 8 bytes per listed       */
+/* record and the scan's own. n_list = 0 returns at once and writes nothing.   */
+/* Size query with workspace == NULL; stream-ordered, no synchronisation.      */
+int bbgr_text_gather(const bbgr_text_gather_args *args, void *workspace,
+                     size_t *workspace_bytes, bbgr_stream_t stream);
+/* For measurement (tools/text_bench.py): the same call with the source fetch  */
+/* picked by `fetch`. UNALIGNED is bbgr_text_gather: one unaligned 16-byte     */
+/* load a word. ALIGNED_PAIR: the one or two 16-byte aligned words that hold   */
+/* the 16 bytes and a byte shift, taken where both words lie inside            */
+/* data[first, last), else the bytes one by one. The same bytes come out.      */
+#define BBGR_TEXT_FETCH_UNALIGNED 0
+#define BBGR_TEXT_FETCH_ALIGNED_PAIR 1
+int bbgr_text_gather_fetch(const bbgr_text_gather_args *args, int32_t fetch, void *workspace,
+                           size_t *workspace_bytes, bbgr_stream_t stream);
 
 /* ------------------------------------------------------------------------- */
 /* Blueprint names (SURVEY §8(b)'s ABI sketch), thin forms of the above.      */

@@ -2,6 +2,7 @@
 
     python tools/text_bench.py [--records 1000000] [--reps 10] [--host-records N]
                                [--jsonl-lines 200000] [--out profiles/text/text_c2.json]
+    python tools/text_bench.py --pooled [--chunk-bytes N [N ..]]
 
 Workload: a seeded synthetic corpus of --records reviews (C2's record count by
 default): Zipf (1 / rank) draws from a vocabulary of 50,000 lower-case words
@@ -242,6 +243,189 @@ def pooled_main(args):
     print(json.dumps(rec))
 
 
+def _alternate(arms: dict, warmup: int, reps: int, clock: str) -> dict:
+    """The arms in turn, round after round in one process (a drift of the
+    clocks hits all alike): per arm the median, min and max of `reps` rounds
+    after `warmup`. clock "events": device events around the call; "host": the
+    host clock between two synchronisations (calls that read back)."""
+    ts = {name: [] for name in arms}
+    for k in range(warmup + reps):
+        for name, fn in arms.items():
+            if clock == "events":
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                fn()
+                b.record()
+                b.synchronize()
+                t = a.elapsed_time(b)
+            else:
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                fn()
+                torch.cuda.synchronize()
+                t = (time.perf_counter() - t0) * 1e3
+            if k >= warmup:
+                ts[name].append(t)
+    return {name: {"median_ms": statistics.median(v), "min_ms": min(v), "max_ms": max(v),
+                   "reps": reps} for name, v in ts.items()}
+
+
+def chunked_main(args):
+    """--pooled --chunk-bytes N [N ..]: what the regrouped pooled count costs,
+    on the --pooled corpus resident on the device. (1) bbgr_text_gather alone
+    over all records in user order beside a device copy_ of as many bytes
+    (which reads and writes every byte once), alternating, with lists that
+    take the search or the misalignment of the source words away (below; the
+    events of a gather arm span the host's ctypes call too, `host_call_us`).
+    (2) The whole
+    pooled_token_counts: the one-chunk call beside chunk_bytes = each N,
+    alternating; an N of at least the text is one range, so its excess over
+    the one-chunk call is the regrouping itself (the CSR build, the gather,
+    the local ids), and the smaller N add the per-range host reads."""
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    from features_bench import synthetic_columns
+    from bbgr.synthetic import CONFIGS
+    out_path = args.out or os.path.join(ROOT, "profiles", "features_v2",
+                                        "text_pooled_chunked_c2.json")
+    U = CONFIGS["C2"]["num_users"]
+    user = np.ascontiguousarray(synthetic_columns("C2").user[:args.records])
+    host_text = synthetic_corpus(len(user))
+    n, nbytes = len(host_text), int(host_text.data.shape[0])
+    dev = torch.device("cuda", torch.cuda.current_device())
+    text = TX.resident(host_text, dev)
+    grp = torch.from_numpy(user).to(dev)
+    off = torch.from_numpy(host_text.offsets).to(dev)
+    rec = {"records": n, "users": U, "text_bytes": nbytes, 
+           "source_fetch": "unaligned 16-byte load; arms *_aligned_pair: two aligned loads + shift",
+           "device": torch.cuda.get_device_name(0), "hbm_peak_TBps": HBM_PEAK / 1e12}
+
+    # (1) the gather alone, all records in user order
+    indptr, eid = FT._group(grp, torch.zeros(n, dtype=torch.int32, device=dev), U)
+    packed = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    other = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    p_off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    p_total = torch.empty(1, dtype=torch.int64, device=dev)
+    ga = _lib.TextGatherArgs()
+    ga.n_list, ga.records, ga.n = n, _lib.ptr(eid), n
+    ga.data, ga.offsets, ga.first, ga.last = _lib.ptr(text.data), _lib.ptr(off), 0, nbytes
+    ga.out_offsets, ga.out_data, ga.capacity = _lib.ptr(p_off), _lib.ptr(packed), nbytes
+    ga.total = _lib.ptr(p_total)
+    keep = _lib.Workspace(grow=False)
+    st = _lib.stream_handle()
+    ga_null = _lib.TextGatherArgs.from_buffer_copy(ga)
+    ga_null.out_data = None
+    # Lists that take parts of the work away. The records in file order: the source is read
+    # front to back. Records of 496 bytes each over the same bytes, in order (REC bytes, the
+    # corpus's mean, a multiple of 16): the search stays, and every source word is 16-byte
+    # aligned when the text starts at 0, off by one byte everywhere when it starts at 1. The
+    # whole text as ONE record: no search (one pair of offsets for all lanes), again aligned
+    # from 0 and off by one from 1. The four make search x alignment.
+    REC = 496
+    file_order = torch.arange(n, dtype=torch.int32, device=dev)
+    ga_file = _lib.TextGatherArgs.from_buffer_copy(ga)
+    ga_file.records = _lib.ptr(file_order)
+    n_fix = (nbytes - 1) // REC
+    fix_order = torch.arange(n_fix, dtype=torch.int32, device=dev)
+    assert text.data.data_ptr() % 16 == 0 and packed.data_ptr() % 16 == 0
+    variants, held = {}, []
+    for name, start, m in (("one_record", 0, 1), ("one_record_off_by_1", 1, 1),
+                           ("fixed_496", 0, n_fix), ("fixed_496_off_by_1", 1, n_fix)):
+        o = (start + REC * torch.arange(m + 1, dtype=torch.int64, device=dev) if m > 1 else
+             torch.tensor([start, nbytes], dtype=torch.int64, device=dev))
+        v = _lib.TextGatherArgs.from_buffer_copy(ga)
+        v.n_list, v.n, v.offsets, v.records = m, m, _lib.ptr(o), _lib.ptr(fix_order)
+        v.first, v.last = start, int(o[-1])
+        held.append(o)
+        variants[name] = (v, _lib.Workspace(grow=False), int(o[-1]) - start)
+
+    def gather_arm(a, ws, fetch=None):
+        if fetch is None:
+            return lambda: _lib.call_with_workspace("bbgr_text_gather", ctypes.byref(a),
+                                                    after=(st,), device=dev, keep=ws)
+        return lambda: _lib.call_with_workspace("bbgr_text_gather_fetch", ctypes.byref(a),
+                                                _lib.TEXT_FETCH[fetch], after=(st,), device=dev,
+                                                keep=ws)
+
+    arms = {"copy": lambda: other.copy_(text.data),
+            "gather_offsets_only": gather_arm(ga_null, keep),
+            "gather_file_order": gather_arm(ga_file, keep)}
+    for name, (v, ws, _) in variants.items():
+        arms["gather_" + name] = gather_arm(v, ws)
+        arms["gather_" + name + "_aligned_pair"] = gather_arm(v, ws, "aligned_pair")
+    # the other source fetch (two aligned loads and a byte shift) on the real lists
+    arms["gather_file_order_aligned_pair"] = gather_arm(ga_file, keep, "aligned_pair")
+    arms["gather_aligned_pair"] = gather_arm(ga, keep, "aligned_pair")
+    arms["gather"] = gather_arm(ga, keep)   # last in a round: the buffers checked below are its
+    g = _alternate(arms, args.warmup, args.reps, "events")
+    assert int(p_total) == nbytes
+    order = eid[:n].long()
+    starts = off[:-1][order]
+    k = int(torch.randint(0, n, (1,)))                      # one record checked byte for byte
+    a0, b0 = int(p_off[k]), int(p_off[k + 1])
+    assert torch.equal(packed[a0:b0], text.data[int(starts[k]):int(starts[k]) + b0 - a0])
+    # the variants copy what they should: the text from its start on
+    for name, (v, ws, moved) in variants.items():
+        gather_arm(v, ws)()
+        assert int(p_total) == moved
+        assert torch.equal(packed[:moved], text.data[v.first:v.first + moved])
+    moved = {}
+    for name, (v, ws, m) in variants.items():
+        moved["gather_" + name] = moved["gather_" + name + "_aligned_pair"] = m
+        gather_arm(v, ws, "aligned_pair")()
+        assert torch.equal(packed[:m], text.data[v.first:v.first + m])
+    g_pair = torch.empty_like(packed)
+    gather_arm(ga, keep)()
+    g_pair.copy_(packed)
+    gather_arm(ga, keep, "aligned_pair")()
+    assert torch.equal(g_pair, packed)                       # both fetches: the same bytes
+    del g_pair
+    for name, r in g.items():
+        if name != "gather_offsets_only":                   # that arm moves no text
+            r["bytes"] = moved.get(name, nbytes)
+            r["TBps_read_plus_write"] = 2 * r["bytes"] / (r["median_ms"] * 1e-3) / 1e12
+        log(name, r)
+    # Between the two events of a gather arm lies the host's ctypes call as well (no size
+    # query: the workspace is kept); the copy arm has none. Its length, from a call that
+    # returns before any launch (n_list = 0), by the host clock:
+    ga_none = _lib.TextGatherArgs.from_buffer_copy(ga)
+    ga_none.n_list = 0
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(200):
+        gather_arm(ga_none, keep)()
+    g["host_call_us"] = (time.perf_counter() - t0) * 1e6 / 200
+    g["gather"]["kernel_ms"] = g["gather"]["median_ms"] - g["gather_offsets_only"]["median_ms"]
+    g["gather_over_copy"] = g["gather"]["median_ms"] / g["copy"]["median_ms"]
+    g["aligned_pair_over_copy"] = g["gather_aligned_pair"]["median_ms"] / g["copy"]["median_ms"]
+    rec["gather"] = g
+    del packed, other, keep
+
+    # (2) the whole call, one chunk beside the regrouped ones
+    calls, infos = {}, {}
+
+    def arm(name, **kw):
+        def run():
+            infos[name] = TX.pooled_token_counts(text, grp, U, dev, **kw)
+        return run
+
+    calls["one_chunk"] = arm("one_chunk")
+    for c in args.chunk_bytes:
+        calls[f"chunk_bytes={c}"] = arm(f"chunk_bytes={c}", chunk_bytes=c)
+    rec["calls"] = _alternate(calls, args.warmup, args.reps, "host")
+    base = infos["one_chunk"]
+    for name, r in rec["calls"].items():
+        tok, uniq, info = infos[name]
+        r["info"] = info
+        r["equals_one_chunk"] = bool(torch.equal(tok, base[0]) and torch.equal(uniq, base[1]))
+        r["over_one_chunk"] = r["median_ms"] / rec["calls"]["one_chunk"]["median_ms"]
+        log(name, r)
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, "w") as f:
+        json.dump(rec, f, indent=1)
+        f.write("\n")
+    print(json.dumps(rec))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--records", type=int, default=1_000_000)
@@ -253,11 +437,16 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--pooled", action="store_true",
                     help="time bbgr.text.pooled_token_counts (distinct tokens per user) instead")
+    ap.add_argument("--chunk-bytes", type=int, nargs="+", default=None,
+                    help="with --pooled: time the regrouped count at these chunk sizes and "
+                         "bbgr_text_gather alone (profiles/features_v2/text_pooled_chunked_c2.json)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("text_bench needs a GPU: no timing is taken without one")
+    if args.chunk_bytes and not args.pooled:
+        raise SystemExit("--chunk-bytes goes with --pooled")
     if args.pooled:
-        return pooled_main(args)
+        return chunked_main(args) if args.chunk_bytes else pooled_main(args)
     out_path = args.out or os.path.join(ROOT, "profiles", "text", "text_c2.json")
     t0 = time.perf_counter()
     text = synthetic_corpus(args.records)

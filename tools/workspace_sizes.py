@@ -67,6 +67,12 @@ def _text(n, n_bytes):
                    n_tokens=FAKE, n_unique_tokens=FAKE, recheck=FAKE, totals=FAKE)
 
 
+def _gather(n_list, n, n_bytes):
+    return _struct(_lib.TextGatherArgs, n_list=n_list, records=FAKE, n=n, data=FAKE, offsets=FAKE,
+                   first=0, last=n_bytes, out_offsets=FAKE, out_data=FAKE, capacity=n_bytes,
+                   total=FAKE)
+
+
 def _jsonl(n_bytes, n_lines):
     return _struct(_lib.JsonlArgs, n_bytes=n_bytes, data=FAKE, n_lines=n_lines, line_end=FAKE,
                    status=FAKE, rating=FAKE, helpful_vote=FAKE, verified=FAKE, timestamp=FAKE,
@@ -164,6 +170,11 @@ CASES = {
          (_text(1000, 100_000), 20_000, FAKE, 50, FAKE, FAKE, FAKE, 2)),
         ("n=1000000,tokens=60000000,groups=400000,all",
          (_text(1_000_000, 400_000_000), 60_000_000, FAKE, 400_000, FAKE, FAKE, FAKE, 7))],
+    "bbgr_text_gather": [("list=1000,n=1000", (_gather(1000, 1000, 100_000),)),
+                         ("list=5000000,n=5000000", (_gather(5_000_000, 5_000_000, 1 << 31),))],
+    "bbgr_text_gather_fetch": [
+        ("list=1000,n=1000,unaligned", (_gather(1000, 1000, 100_000), 0)),
+        ("list=5000000,n=5000000,aligned pair", (_gather(5_000_000, 5_000_000, 1 << 31), 1))],
     "bbgr_jsonl_lines": [("bytes=100000,lines=300", (_jsonl(100_000, 300),)),
                          ("bytes=2000000000,lines=3000000", (_jsonl(2_000_000_000, 3_000_000),))],
     "bbgr_jsonl_offsets": [("bytes=100000,lines=300", (_jsonl(100_000, 300),)),
